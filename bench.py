@@ -8,13 +8,18 @@ RCCL, then one libmavg launch over this rank's 2^30-sample shard, inputs
 already resident in HBM (generated on the device by the counter-based
 synthetic generator).  Weak scaling: 2^30 samples per GPU.
 
-    python bench.py                      # N=1, default K/W
+    python bench.py                      # N=1, default K/W: the headline figure only
+    python bench.py --full               # + copy ceiling, CPU baselines (N>1: single-launch scaling detail)
+    python bench.py --dump-outputs DIR   # + DIR/y.npy: a fixed sample of the last timed step's output
     python bench.py --gpus N             # spawns N ranks itself (one process per GPU)
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
 
 Rank 0 prints ONE JSON line (contract in the task statement), with
-`roofline` (dominant kernel, algorithmic bytes / HIP-event kernel time vs
-8 TB/s) and `cpu_baseline` (oracle restatement on a bounded sample, 1 core).
+`roofline` (dominant kernel, algorithmic bytes / HIP-event kernel time of
+the timed steps vs 8 TB/s).  A plain run sets up, wakes the device, warms up,
+times the steps and prints that line.  What takes runs of its own is behind
+--full: `copy_ceiling` (the same-box streaming copy, timed), `cpu_baseline`
+(oracle restatement on one core and on many) and, N > 1, `scaling_detail`.
 """
 from __future__ import annotations
 
@@ -95,7 +100,14 @@ def parse(argv=None):
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--workload", default="headline", choices=sorted(WORKLOADS))
     ap.add_argument("--algo", default=None, help="override the workload's algorithm")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the timed copy ceiling, the CPU "
+                         "baselines (N=1) and the single-launch scaling detail (N>1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write a fixed sample of the last timed step's output as "
+                         "DIR/y.npy (float32; N>1: DIR/y_rank<r>.npy per rank): the head and the tail of the "
+                         "signal and seeded spans between them")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
     ap.add_argument("--cpu-samples", type=int, default=1 << 30,
                     help="CPU-baseline sample (samples; default: the whole 2^30 headline signal, SURVEY.md 8d)")
     ap.add_argument("--cpu-reps", type=int, default=3)
@@ -138,16 +150,21 @@ def rank_env(base: dict, rank: int, world: int, port: int) -> dict:
     return env
 
 
+def with_cpu_baseline(args, world: int) -> bool:
+    """The CPU baselines run under --full on a single GPU, unless --no-cpu-baseline."""
+    return args.full and world == 1 and not args.no_cpu_baseline
+
+
 def run_deadline(args) -> float:
     """Seconds `bench.py --gpus N` (self-launched ranks) may run before the
     parent kills its ranks: the rendezvous and one stuck phase (each rank's
     own watchdog fires first), plus, per workload, its warm-up and timed steps
     twice over (the sharded steps, then shard_timing's single launches) at a
     generous 50 ms each, the copy calibration, the check and the all-gathers,
-    plus the CPU baseline's repetitions where one runs (N = 1 only)."""
+    plus the CPU baseline's repetitions where one runs (--full, N = 1 only)."""
     n_work = len(WORKLOADS) if args.all_workloads else 1
     per_workload = 60.0 + (2 * args.steps + 2 * args.warmup) * 0.05
-    cpu = 0.0 if (args.no_cpu_baseline or args.gpus > 1) else 30.0 * (args.cpu_reps + max(3, args.cpu_reps))
+    cpu = 30.0 * (args.cpu_reps + max(3, args.cpu_reps)) if with_cpu_baseline(args, args.gpus) else 0.0
     return args.init_timeout + args.phase_timeout + n_work * per_workload + cpu
 
 
@@ -405,6 +422,30 @@ def check_output(y, n, k, C, dt, seed, rank, samples=64, span=4096):
     return {"slices": len(starts), "span_frames": span, "mismatches": bad}
 
 
+DUMP_MAX_SAMPLES = 1 << 22  # 16 MiB of float32 per rank
+DUMP_SPANS = 256
+
+
+def dump_outputs(path_dir, y, C, rank, world):
+    """--dump-outputs: this rank's output of the last timed step as float32
+    (int16 values are exact in it), whole if it has at most DUMP_MAX_SAMPLES
+    samples, else DUMP_SPANS spans of whole frames: the head of the signal
+    (the partial windows), its tail, and spans at fixed seeded offsets between
+    them, in signal order.  The sample depends on the shape alone."""
+    import numpy as np
+    import torch
+    n = y.numel()
+    if n > DUMP_MAX_SAMPLES:
+        frames = n // C
+        span = max(1, DUMP_MAX_SAMPLES // DUMP_SPANS // C)
+        rng = np.random.default_rng(0x5EED)
+        starts = sorted({0, frames - span, *(int(s) for s in rng.integers(0, frames - span, DUMP_SPANS - 2))})
+        y = torch.cat([y[s * C:(s + span) * C] for s in starts])
+    os.makedirs(path_dir, exist_ok=True)
+    name = "y.npy" if world == 1 else f"y_rank{rank}.npy"
+    np.save(os.path.join(path_dir, name), y.to(torch.float32).cpu().numpy())
+
+
 def shard_timing(args, x, y, k, C, algo, ev, hev, value, n, rank, world):
     """N > 1: what the sharded step costs each rank beyond one plain launch.
     Per rank, from the timed steps' events on the launch stream: the halo wait
@@ -488,25 +529,33 @@ def comm_report(rank: int, world: int, halo_bytes: int) -> dict:
     return rccl_block(every, dist.get_backend(), version, halo_bytes, dist.get_world_size())
 
 
-def copy_ceiling(xs, ys, rot, steps, world, min_s=0.25):
+def copy_ceiling(xs, ys, rot, steps, world, min_s=0.25, timed=True):
     """Mean per-launch time (ms) of the library's calibration copy over the
     workload's buffers, at least `steps` launches and `min_s` seconds of them
-    (max over ranks), and the number of launches timed."""
+    (max over ranks), and the number of launches timed.  `timed=False`: the
+    same launches as the device's wake-up only, no events and no figure (None)."""
     import torch
     import digital_signal_processsing_amd as dsp
     for w in range(3):
         dsp.stream_copy(xs[w % rot], ys[w % rot])
     torch.cuda.synchronize()
-    times, t0 = [], time.perf_counter()
-    while len(times) < steps or time.perf_counter() - t0 < min_s:
-        ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(steps)]
-        for i, (a, b) in enumerate(ev):
-            a.record()
+    times, launches, t0 = [], 0, time.perf_counter()
+    while launches < steps or time.perf_counter() - t0 < min_s:
+        ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) if timed else None
+              for _ in range(steps)]
+        for i, e in enumerate(ev):
+            if timed:
+                e[0].record()
             dsp.stream_copy(xs[i % rot], ys[i % rot])
-            b.record()
+            if timed:
+                e[1].record()
         torch.cuda.synchronize()
-        times += [a.elapsed_time(b) for a, b in ev]
-    return max_over_ranks(statistics.mean(times), world), len(times), time.perf_counter() - t0
+        launches += len(ev)
+        if timed:
+            times += [a.elapsed_time(b) for a, b in ev]
+    if not timed:
+        return None, launches, time.perf_counter() - t0
+    return max_over_ranks(statistics.mean(times), world), launches, time.perf_counter() - t0
 
 
 def halo_progress(hev):
@@ -558,10 +607,12 @@ def run_workload(args, name, rank, world, with_cpu, wd=None):
     # otherwise still timed on the clock ramp (i16_c4_2p30 0.670 of peak after
     # 5 warm-up steps, 0.777 after 200; the headline 0.786 / 0.807;
     # profiles/r05_validation/warmup_ramp/).  The timed region is unchanged.
+    # A plain run needs only that wake-up: it issues the same launches without
+    # events and reports no ceiling; --full times them (`copy_ceiling`).
     wd = wd or _NoWatchdog()
     pt = args.phase_timeout
     with wd.phase(f"{name}: copy calibration (all-reduce)", pt):
-        copy_ms, copy_launches, copy_s = copy_ceiling(xs, ys, rot, args.steps, world)
+        copy_ms, copy_launches, copy_s = copy_ceiling(xs, ys, rot, args.steps, world, timed=args.full)
 
     def step(i=None, j=0):
         if world > 1:
@@ -647,6 +698,10 @@ def run_workload(args, name, rank, world, with_cpu, wd=None):
                       "the head launch are outside it and only in value / ms_per_step"),
         },
     }
+    if args.dump_outputs and name == args.workload:
+        wd.set(f"{name}: dump of the outputs", pt)
+        last = (args.steps - 1) % rot if args.steps else 0
+        dump_outputs(args.dump_outputs, ys[last], C, rank, world)
     if args.check:
         wd.set(f"{name}: check against the oracle", pt)
         res = check_output(y, n, k, C, dt, seed, rank)
@@ -661,28 +716,29 @@ def run_workload(args, name, rank, world, with_cpu, wd=None):
     if world > 1:
         wd.set(f"{name}: all-gather of the device records", pt)
         line["rccl"] = comm_report(rank, world, (k - 1) * C * elem)
-    if world > 1:  # after --check: the single launches overwrite the output with a no-halo result
+    if world > 1 and args.full:  # after --check and the dump: the single launches overwrite the output with a no-halo result
         wd.set(f"{name}: single-launch timing (barrier, all-gather)", pt)
         line["scaling_detail"] = shard_timing(args, x, y, k, C, algo, ev, hev, value, n, rank, world)
     wd.set(f"{name}: report", None)
-    copy_gbs = 2 * elem * n / (copy_ms * 1e-3) / 1e9
-    line["copy_ceiling"] = {
-        "kernel": "mavg_stream_copy: flat grid, one 16-B non-temporal load + store per thread",
-        "achieved": round(copy_gbs, 1),
-        "unit": "GB/s",
-        "frac": round(copy_gbs / HBM_PEAK_GBS, 4),
-        "kernel_avg_ms": round(copy_ms, 4),
-        "launches": copy_launches,
-        "seconds": round(copy_s, 3),
-        "when": "measured before the workload's warm-up steps, over at least --steps launches and 0.25 s",
-    }
+    if args.full:
+        copy_gbs = 2 * elem * n / (copy_ms * 1e-3) / 1e9
+        line["copy_ceiling"] = {
+            "kernel": "mavg_stream_copy: flat grid, one 16-B non-temporal load + store per thread",
+            "achieved": round(copy_gbs, 1),
+            "unit": "GB/s",
+            "frac": round(copy_gbs / HBM_PEAK_GBS, 4),
+            "kernel_avg_ms": round(copy_ms, 4),
+            "launches": copy_launches,
+            "seconds": round(copy_s, 3),
+            "when": "measured before the workload's warm-up steps, over at least --steps launches and 0.25 s",
+        }
+        line["roofline"]["frac_of_copy"] = round(achieved / copy_gbs, 4)
     # what ran on the device before the timed steps (bench lines from round 5 on: the copy
     # calibration first, which also takes the device out of its idle clocks; earlier rounds'
     # lines had only the W warm-up steps -- DESIGN.md "The start of a process")
     line["warmup_detail"] = {"copy_calibration_launches": copy_launches, "copy_calibration_s": round(copy_s, 3),
                              "workload_warmup_steps": args.warmup}
-    line["roofline"]["frac_of_copy"] = round(achieved / copy_gbs, 4)
-    if with_cpu and rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if with_cpu and rank == 0 and with_cpu_baseline(args, world):
         line["cpu_baseline"], line["cpu_baseline_multicore"] = cpu_baseline(args, n, k, C, seed)
     del x, y, xs, ys
     torch.cuda.empty_cache()

@@ -58,7 +58,7 @@ def test_bench_self_launch_two_ranks_gloo_check(gpu):
     step and check their shards, including each shard head, against the
     oracle; rank 0 prints exactly one JSON line."""
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dist-backend", "gloo",
-                        "--steps", "3", "--warmup", "1", "--check"], env=_clean_env(), capture_output=True,
+                        "--steps", "3", "--warmup", "1", "--check", "--full"], env=_clean_env(), capture_output=True,
                        text=True, timeout=110)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
@@ -95,3 +95,35 @@ def test_rccl_block_requires_distinct_devices_under_nccl():
     assert not bench.rccl_block([_rec(0, "a"), _rec(1, "a")], "gloo", None, 4092, 2)["distinct_devices"]
     # the same UUID string on two hosts is two devices
     assert bench.rccl_block([_rec(0, "a", "h0"), _rec(1, "a", "h1")], "nccl", None, 8, 2)["distinct_devices"]
+
+
+def test_full_is_off_by_default_and_gates_the_cpu_baseline():
+    import bench
+    plain = bench.parse(["--gpus", "1", "--steps", "3", "--warmup", "1"])
+    assert not plain.full and plain.dump_outputs is None and not bench.with_cpu_baseline(plain, 1)
+    assert bench.with_cpu_baseline(bench.parse(["--full"]), 1)
+    assert not bench.with_cpu_baseline(bench.parse(["--full", "--no-cpu-baseline"]), 1)
+    assert not bench.with_cpu_baseline(bench.parse(["--full", "--gpus", "2"]), 2)
+
+
+@pytest.mark.parametrize("C", [1, 3])
+def test_dump_outputs_is_a_fixed_sample_with_head_and_tail(tmp_path, C):
+    """--dump-outputs: float32, the same sample on every call, whole frames in
+    signal order, the head and the tail of the signal among them, and far
+    below 64 MB; a small output is written whole."""
+    import numpy as np
+    import torch
+    import bench
+    frames = bench.DUMP_MAX_SAMPLES // C + 12345
+    y = (torch.arange(frames * C, dtype=torch.int32) % 30011).to(torch.int16)
+    bench.dump_outputs(str(tmp_path / "a"), y, C, 0, 1)
+    bench.dump_outputs(str(tmp_path / "b"), y, C, 1, 2)
+    a, b = np.load(tmp_path / "a" / "y.npy"), np.load(tmp_path / "b" / "y_rank1.npy")
+    assert a.dtype == np.float32 and np.array_equal(a, b)
+    span = bench.DUMP_MAX_SAMPLES // bench.DUMP_SPANS // C * C
+    assert a.size % span == 0 and 0 < a.nbytes <= 4 * bench.DUMP_MAX_SAMPLES < 64 << 20
+    ref = y.numpy().astype(np.float32)
+    assert np.array_equal(a[:span], ref[:span]) and np.array_equal(a[-span:], ref[-span:])
+    small = y[: 5 * C]
+    bench.dump_outputs(str(tmp_path / "c"), small, C, 0, 1)
+    assert np.array_equal(np.load(tmp_path / "c" / "y.npy"), ref[: 5 * C])

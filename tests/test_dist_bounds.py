@@ -90,8 +90,9 @@ def test_run_deadline_is_finite_and_grows_with_the_work():
     assert a.init_timeout + a.phase_timeout < d < 600, d  # inside the driver's limit by default
     b = bench.parse(["--gpus", "8", "--steps", "2000"])
     assert bench.run_deadline(b) > d
-    c = bench.parse(["--gpus", "1"])  # the CPU baseline's reps count where it runs
-    assert bench.run_deadline(c) > bench.run_deadline(bench.parse(["--gpus", "1", "--no-cpu-baseline"]))
+    c = bench.parse(["--gpus", "1", "--full"])  # the CPU baseline's reps count where it runs
+    assert bench.run_deadline(c) > bench.run_deadline(bench.parse(["--gpus", "1", "--full", "--no-cpu-baseline"]))
+    assert bench.run_deadline(c) > bench.run_deadline(bench.parse(["--gpus", "1"]))
 
 
 @pytest.mark.parametrize("phases,want", [

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Markdown table of a `bench.py --all-workloads` run: one row per JSON line
+"""Markdown table of a `bench.py --all-workloads --full` run: one row per JSON line
 (stdout's headline and stderr's secondary lines, in one file), with the kernel
 family, Gsamples/s, fraction of 8 TB/s, fraction of the same-box copy and the
 PMC traffic ratio from a traffic.json (tools/pmc_traffic.py).

@@ -7,7 +7,7 @@ OUT=gpurun_out/${1:?session tag}
 shift
 mkdir -p "$OUT"
 for w in "$@"; do
-  timeout -k 10 150 python -u bench.py --workload "$w" --steps 20 --warmup 5 --no-cpu-baseline \
+  timeout -k 10 150 python -u bench.py --workload "$w" --steps 20 --warmup 5 --full --no-cpu-baseline \
     > "$OUT/bench_$w.json" 2> "$OUT/bench_$w.err"
   rc=$?
   python3 -c "import json,sys; d=json.load(open(sys.argv[1])); r=d['roofline']; print(sys.argv[2], d['value'], r['frac'], r['frac_of_copy'], r['kernel'])" "$OUT/bench_$w.json" "$w"

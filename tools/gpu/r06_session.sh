@@ -33,14 +33,14 @@ for s in "$@"; do
     ab_i16_c8) run ab_i16_c8 300 tools/tune/wide_ab 30 44100 8 6 0 i16 ;;
     gpu_tests) run gpu_tests 1100 $PYT --timeout 300 -m gpu tests/ ;;
     bench) run bench 300 python -u bench.py --gpus 1 --steps 20 --warmup 5 ;;
-    bench_all) run bench_all 900 python -u bench.py --steps 20 --warmup 5 --all-workloads --no-cpu-baseline ;;
+    bench_all) run bench_all 900 python -u bench.py --steps 20 --warmup 5 --all-workloads --full --no-cpu-baseline ;;
     wab:*) IFS=: read -r _ k c dt mode <<< "$s"
            [ "$mode" = "-" ] && mode=""
            run "wab_${dt}_c${c}_k${k}_${mode:-default}" 300 tools/tune/wide_ab 30 "$k" "$c" 6 0 "$dt" $mode ;;
     pt:*) IFS=: read -r _ f expr <<< "$s"
           run "pt_$(basename "$f" .py)_$(echo "$expr" | tr -c 'A-Za-z0-9' '_' | cut -c1-40)" 1000 \
               $PYT --timeout 300 -m gpu "tests/$f" -k "$expr" ;;
-    b:*) w=${s#b:}; run "bench_$w" 200 python -u bench.py --workload "$w" --steps 20 --warmup 5 --no-cpu-baseline ;;
+    b:*) w=${s#b:}; run "bench_$w" 200 python -u bench.py --workload "$w" --steps 20 --warmup 5 --full --no-cpu-baseline ;;
     *) echo "unknown step $s"; exit 2 ;;
   esac
 done

@@ -31,7 +31,7 @@ for step in "$@"; do
             -p no:cacheprovider ;;
     testm) run pytest_gpu 1000 python -u -m pytest tests -m gpu -v --maxfail=10 --timeout 200 --timeout-method thread \
             -p no:cacheprovider ;;
-    bench) run bench 400 python bench.py --steps 20 --warmup 5 --all-workloads ;;
+    bench) run bench 400 python bench.py --steps 20 --warmup 5 --all-workloads --full ;;
     prof) run prof 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof" -o run -- \
             python bench.py --steps 10 --warmup 3 --no-cpu-baseline --all-workloads ;;
     pmc) run pmc_fetch 400 rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$OUT/pmc_fetch" -o run -- \
@@ -40,9 +40,9 @@ for step in "$@"; do
             python bench.py --steps 5 --warmup 2 --no-cpu-baseline --all-workloads ;;
     check) run check1 400 python bench.py --steps 5 --warmup 2 --no-cpu-baseline --check --all-workloads ;;
     dist) run dist2 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 \
-            --master-port 29511 bench.py --gpus 2 --steps 5 --warmup 2 --dist-backend gloo --check &&
+            --master-port 29511 bench.py --gpus 2 --steps 5 --warmup 2 --dist-backend gloo --check --full &&
           run dist4 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node 4 --master-addr 127.0.0.1 \
-            --master-port 29512 bench.py --gpus 4 --steps 3 --warmup 1 --dist-backend gloo --check ;;
+            --master-port 29512 bench.py --gpus 4 --steps 3 --warmup 1 --dist-backend gloo --check --full ;;
     dist2) run pytest_dist2 600 python -u -m pytest tests/test_gpu_fullsize.py -m gpu -k rounding -s -q \
             --timeout 170 --timeout-method thread -p no:cacheprovider ;;
     full) run pytest_full 900 python -u -m pytest tests/test_gpu_fullsize.py tests/test_bench_launch.py -m gpu -x -v \
