@@ -66,28 +66,43 @@ int validate(size_t n, int C, int k, int dtype, int algo, int block) {
   return MAVG_OK;
 }
 
+// The flat non-temporal copy (one thread per 16 B) of any size: launches of at
+// most kMaxLaunchItems work-items each (the runtime's limit is on work-items,
+// mavg_launch.hpp), every one over its own part of the views.
+long long flat_copy_launches(size_t bytes) {
+  return ((long long)(bytes / 16) + kMaxLaunchItems - 1) / kMaxLaunchItems;
+}
+
+int launch_flat_copy(const void* in, void* out, size_t bytes, hipStream_t s) {
+  static_assert(kMaxLaunchItems % kWG == 0, "whole workgroups per launch");
+  const long long n = (long long)(bytes / 16);
+  for (long long b = 0; b < n; b += kMaxLaunchItems) {
+    const long long m = std::min(kMaxLaunchItems, n - b);
+    hipLaunchKernelGGL(stream_copy_kernel<u32x4>, dim3((unsigned)((m + kWG - 1) / kWG)), dim3(kWG), 0, s,
+                       static_cast<const u32x4*>(in) + b, static_cast<u32x4*>(out) + b, m);
+    if (hipGetLastError() != hipSuccess) return MAVG_ERR_HIP;
+  }
+  return MAVG_OK;
+}
+
 // k = 1: y = x / 1 = x exactly, for every algorithm and dtype (the window is
 // the sample itself; no history).  A copy instead of a scan: a telescoped
 // running sum loses up to ~1e-6 relative on mixed-scale fp32 data at k = 1
 // (neighbours 2^30 times larger round the differences), a copy loses nothing.
 // The flat non-temporal copy when both views are 16-B aligned, else hipMemcpyAsync.
 int launch_identity(int dtype, int C, const Sig& sg, hipStream_t s) {
+  if ((size_t)sg.nframes > (SIZE_MAX / 4) / (size_t)C) return MAVG_ERR_UNSUPPORTED;  // the byte count stays in size_t
   const size_t bytes = (size_t)sg.nframes * (size_t)C * elem_size(dtype);
   const bool flat = aligned(sg.in, 16) && aligned(sg.out, 16) && bytes % 16 == 0;
   if (g_plan) {
-    snprintf(g_plan->text, sizeof(g_plan->text), "copy<%s,C=%d> (k=1: y = x) bytes=%zu %s",
-             dtype == MAVG_F32 ? "f32" : "i16", C, bytes, flat ? "flat nt 16-B" : "hipMemcpyAsync");
+    const int len = snprintf(g_plan->text, sizeof(g_plan->text), "copy<%s,C=%d> (k=1: y = x) bytes=%zu %s",
+                             dtype == MAVG_F32 ? "f32" : "i16", C, bytes, flat ? "flat nt 16-B" : "hipMemcpyAsync");
+    if (flat && flat_copy_launches(bytes) > 1)
+      snprintf(g_plan->text + len, sizeof(g_plan->text) - len, " launches=%lld", flat_copy_launches(bytes));
     return MAVG_OK;
   }
   if (bytes == 0) return MAVG_OK;
-  if (flat) {
-    const long long n = (long long)(bytes / 16);
-    const long long grid = (n + kWG - 1) / kWG;
-    if (grid > 0x7fffffffLL) return MAVG_ERR_UNSUPPORTED;
-    hipLaunchKernelGGL(stream_copy_kernel<u32x4>, dim3((unsigned)grid), dim3(kWG), 0, s,
-                       static_cast<const u32x4*>(sg.in), static_cast<u32x4*>(sg.out), n);
-    return hipGetLastError() == hipSuccess ? MAVG_OK : MAVG_ERR_HIP;
-  }
+  if (flat) return launch_flat_copy(sg.in, sg.out, bytes, s);
   return hipMemcpyAsync(sg.out, sg.in, bytes, hipMemcpyDeviceToDevice, s) == hipSuccess ? MAVG_OK : MAVG_ERR_HIP;
 }
 
@@ -307,12 +322,7 @@ int mavg_stream_copy(const void* d_in, void* d_out, size_t bytes, void* stream) 
   if (bytes == 0) return MAVG_OK;
   if (d_in == nullptr || d_out == nullptr || bytes % 16 != 0) return MAVG_ERR_INVALID_ARG;
   if (!aligned(d_in, 16) || !aligned(d_out, 16)) return MAVG_ERR_MISALIGNED;
-  const long long n = (long long)(bytes / 16);
-  const long long grid = (n + kWG - 1) / kWG;
-  if (grid > 0x7fffffffLL) return MAVG_ERR_UNSUPPORTED;
-  hipLaunchKernelGGL(stream_copy_kernel<u32x4>, dim3((unsigned)grid), dim3(kWG), 0, static_cast<hipStream_t>(stream),
-                     static_cast<const u32x4*>(d_in), static_cast<u32x4*>(d_out), n);
-  return hipGetLastError() == hipSuccess ? MAVG_OK : MAVG_ERR_HIP;
+  return launch_flat_copy(d_in, d_out, bytes, static_cast<hipStream_t>(stream));
 }
 
 }  // extern "C"

@@ -23,6 +23,19 @@ constexpr size_t kLdsBudget = 64 * 1024;  // per workgroup; keeps >= 2 workgroup
 // A 1024-thread workgroup may take 80 KiB: two of them still fill a CU's 32
 // wave slots within its 160 KiB of LDS.
 constexpr size_t lds_budget(int wg) { return wg >= 1024 ? 80 * 1024 : kLdsBudget; }
+// Work-items (gridDim.x * blockDim.x) of one launch.  The HIP runtime refuses
+// more than 2^32 - 1 in a dimension, however few the workgroups; the kernels
+// that run one thread per sample or per 16 B (naive, the flat copy) cover a
+// longer signal with several launches of at most this many, each given its
+// first index.  The tile, look-ahead and direct kernels run many frames per
+// thread and make one launch: past the limit they return MAVG_ERR_UNSUPPORTED
+// (grid_too_large), in plan mode too and before anything is enqueued -- the
+// frame-unit forms (one frame per lane, two or four per thread) from 2^33 or
+// 2^34 frames, the 16-B-unit forms past what one device holds.
+constexpr long long kMaxLaunchItems = 1LL << 31;
+constexpr bool grid_too_large(long long groups, int wg) {
+  return groups > 0x7fffffffLL || groups * wg > 0xffffffffLL;
+}
 
 int device_cu_count();
 OutParams make_out_params(int k);
@@ -129,7 +142,7 @@ int launch_tile_scan(const Sig& sg, int k, hipStream_t st, int xcd_remap = kRema
   const size_t stage = (((size_t)(p.halo_units + U * WG + 1) * VE * sizeof(T)) + 15) & ~(size_t)15;
   const size_t lds = stage + (size_t)(NSEG + WG / 64) * C * sizeof(A);
   if (lds > lds_budget(WG)) return MAVG_ERR_UNSUPPORTED;
-  if (p.ntiles > 0x7fffffffLL) return MAVG_ERR_UNSUPPORTED;
+  if (grid_too_large(p.ntiles, WG)) return MAVG_ERR_UNSUPPORTED;
   if (g_plan) {
     snprintf(g_plan->text, sizeof(g_plan->text),
              "tile_scan<%s,acc=%s,C=%d,F=%d,U=%d,%s,nt=%d,rc=%d,dv=%d,dma=%d> grid=%lld block=%d lds=%zu "
@@ -163,7 +176,7 @@ int launch_wide_tile(const Sig& sg, int k, hipStream_t st, int xcd_remap = kRema
   const size_t lds = (size_t)(Hg + TG) * 16 + (size_t)(NSEG + WG / 64) * C * sizeof(A);
   if (lds > 80 * 1024) return MAVG_ERR_UNSUPPORTED;  // two workgroups per CU at the longest halos
   const long long ntiles = (nframes + TF - 1) / TF;
-  if (ntiles > 0x7fffffffLL) return MAVG_ERR_UNSUPPORTED;
+  if (grid_too_large(ntiles, WG)) return MAVG_ERR_UNSUPPORTED;
   if (g_plan) {
     snprintf(g_plan->text, sizeof(g_plan->text),
              "wide_tile<%s,acc=%s,C=%d,P=%d,U=%d,nt=%d,dv=%d> grid=%lld block=%d lds=%zu tile_frames=%d remap=%d",
@@ -212,7 +225,7 @@ int launch_chan_tile(const Sig& sg, int k, hipStream_t st, int xcd_remap = kRema
   const size_t lds = (size_t)(Hg + (XG ? 0 : TG)) * 16 + (size_t)2 * NW * C * sizeof(A);
   if (lds > 80 * 1024) return MAVG_ERR_UNSUPPORTED;
   const long long ntiles = (nframes + TF - 1) / TF;
-  if (ntiles > 0x7fffffffLL) return MAVG_ERR_UNSUPPORTED;
+  if (grid_too_large(ntiles, WG)) return MAVG_ERR_UNSUPPORTED;
   const bool ip = XG && IPOK && Hg * EPG == (long long)k * C;  // staged halo frames Hg EPG / C == k
   if (g_plan) {
     snprintf(g_plan->text, sizeof(g_plan->text),
@@ -359,7 +372,7 @@ int launch_ahead_scan(const Sig& sg, int k, hipStream_t st, Workspace ws, int ah
   constexpr size_t kStageBytes = (((size_t)(U * WG + 1) * VE * sizeof(T)) + 15) & ~(size_t)15;
   const long long ntiles = (nframes + TF - 1) / TF;
   const long long nfull = nframes / TF;
-  if (ntiles > 0x7fffffffLL) return MAVG_ERR_UNSUPPORTED;
+  if (grid_too_large(ntiles, WG)) return MAVG_ERR_UNSUPPORTED;
   // runs with a published total: run r's is published with the record of
   // the last tile of run r + 8, which must be a whole tile of a complete
   // period (remap_tile maps the blocks past those to themselves)
@@ -567,7 +580,7 @@ int launch_wide_ahead(const Sig& sg, int k, hipStream_t st, Workspace ws, int ah
   const int xcd_remap = ahead_past_l2(k, C, sizeof(T), TF) ? ahead_run_length(k, TF, ahead_plan) : 1;
   const long long ntiles = (nframes + TF - 1) / TF;
   const long long nfull = nframes / TF;
-  if (ntiles > 0x7fffffffLL) return MAVG_ERR_UNSUPPORTED;
+  if (grid_too_large(ntiles, WG)) return MAVG_ERR_UNSUPPORTED;
 #ifdef MAVG_AHEAD_TRACE
   const size_t trace_bytes = (size_t)ntiles * 64;  // tuning builds: 8 stamps per tile, after the stats
 #else
@@ -950,7 +963,7 @@ int launch_direct(const Sig& sg, int k, hipStream_t st, int xcd_remap = kRemapGr
   const size_t lds = (((size_t)(p.m + U * WG) * VE * sizeof(T)) + 15) & ~(size_t)15;
   if (lds > kLdsBudget) return MAVG_ERR_UNSUPPORTED;
   const long long nblk = (nframes + TF - 1) / TF;
-  if (nblk > 0x7fffffffLL) return MAVG_ERR_UNSUPPORTED;
+  if (grid_too_large(nblk, WG)) return MAVG_ERR_UNSUPPORTED;
   if (g_plan) {
     snprintf(g_plan->text, sizeof(g_plan->text), "direct<%s,acc=%s,C=%d,F=%d,U=%d,nt=%d> grid=%lld block=%d lds=%zu",
              type_name<T>(), type_name<A>(), C, F, U, NT, nblk, WG, lds);
@@ -1024,17 +1037,25 @@ int dispatch_direct(int C, int width, const Sig& sg, int k, int block, hipStream
 template <typename T, typename A>
 int launch_naive(const Sig& sg, int C, int k, int block, hipStream_t st) {
   const int wg = block == 0 ? kWG : block;
+  if (sg.nframes > (1LL << 62) / C) return MAVG_ERR_UNSUPPORTED;  // the sample index stays in int64
   const long long n = sg.nframes * C;
   const long long nblk = (n + wg - 1) / wg;
-  if (nblk > 0x7fffffffLL) return MAVG_ERR_UNSUPPORTED;
+  // one thread per sample: launches of at most kMaxLaunchItems work-items (whole workgroups)
+  const long long per = kMaxLaunchItems / wg;
+  const long long launches = (nblk + per - 1) / per;
   if (g_plan) {
-    snprintf(g_plan->text, sizeof(g_plan->text), "naive<%s,acc=%s> grid=%lld block=%d", type_name<T>(),
-             type_name<A>(), nblk, wg);
+    int len = snprintf(g_plan->text, sizeof(g_plan->text), "naive<%s,acc=%s> grid=%lld block=%d", type_name<T>(),
+                       type_name<A>(), nblk, wg);
+    if (launches > 1) snprintf(g_plan->text + len, sizeof(g_plan->text) - len, " launches=%lld", launches);
     return MAVG_OK;
   }
-  hipLaunchKernelGGL((naive_kernel<T, A>), dim3((unsigned)nblk), dim3(wg), 0, st, static_cast<const T*>(sg.in),
-                     static_cast<T*>(sg.out), static_cast<const T*>(sg.hist), sg.nframes, C, k, make_out_params(k));
-  return hipGetLastError() == hipSuccess ? MAVG_OK : MAVG_ERR_HIP;
+  for (long long b = 0; b < nblk; b += per) {
+    hipLaunchKernelGGL((naive_kernel<T, A>), dim3((unsigned)std::min(per, nblk - b)), dim3(wg), 0, st,
+                       static_cast<const T*>(sg.in), static_cast<T*>(sg.out), static_cast<const T*>(sg.hist),
+                       sg.nframes, C, k, make_out_params(k), b * wg);
+    if (hipGetLastError() != hipSuccess) return MAVG_ERR_HIP;
+  }
+  return MAVG_OK;
 }
 
 }  // namespace mavg

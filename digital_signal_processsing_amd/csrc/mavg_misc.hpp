@@ -8,13 +8,15 @@ namespace mavg {
 // ----------------------------------------------------------------------------
 // naive kernel: one thread per sample, k reads from global memory
 // (profilable_parallel_averager.cu:14-23, with the history contract instead
-// of reading before the buffer).
+// of reading before the buffer).  `base`: the sample index of this launch's
+// first thread (launch_naive splits a signal of more work-items than one
+// launch may hold).
 // ----------------------------------------------------------------------------
 template <typename T, typename A>
 __global__ __launch_bounds__(1024) void naive_kernel(const T* __restrict__ in, T* __restrict__ out,
                                                      const T* __restrict__ hist, long long nframes,
-                                                     int C, int k, OutParams o) {
-  const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+                                                     int C, int k, OutParams o, long long base) {
+  const long long idx = base + (long long)blockIdx.x * blockDim.x + threadIdx.x;
   const long long n = nframes * C;
   if (idx >= n) return;
   const long long f = idx / C;

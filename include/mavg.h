@@ -116,6 +116,24 @@ int mavg_workspace_bytes(size_t n_samples, int channels, int grade, int dtype,
  *   stream     hipStream_t or NULL.
  * Returns a mavg_status.  Nothing is enqueued unless MAVG_OK is returned
  * (MAVG_ERR_HIP excepted, when the launch itself failed).
+ *
+ * Supported maximum.  n_samples / channels < 2^62 frames, and one launch
+ * holds at most 2^32 - 1 work-items (the HIP runtime's limit):
+ *   - MAVG_ALGO_NAIVE (one thread per sample), the k = 1 copy and
+ *     mavg_stream_copy (one thread per 16 B) cover a longer signal with
+ *     several launches of 2^31 work-items: every size below 2^62 samples
+ *     (mavg_plan shows "launches=" when there is more than one);
+ *   - every other kernel makes one launch of `block` threads per
+ *     `tile_frames` frames (both in mavg_plan's text; the direct kernels:
+ *     U * F frames per thread), so it takes
+ *         frames <= (2^32 - 1) / block * tile_frames:
+ *     the tuned 16-B-unit forms 2^35 frames and more (fp32 mono k = 1024:
+ *     8 frames per thread), the frame-unit forms (*_SCALAR, frames that do
+ *     not divide 16 B, views off 16-B alignment by different amounts) 2 or 4
+ *     frames per thread: 2^33 or 2^34 frames.  Past it mavg_run and mavg_plan
+ *     return MAVG_ERR_UNSUPPORTED and nothing is enqueued.
+ * Every kernel family is tested on 2^32 + 10^6-sample signals
+ * (tests/test_gpu_bigsignal.py).
  */
 int mavg_run(const void* d_in, void* d_out, size_t n_samples, int channels,
              int grade, int dtype, int algo, int block_size,
