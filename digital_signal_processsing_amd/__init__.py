@@ -7,6 +7,7 @@ only for device memory and streams.
 
     y = moving_average(x, grade=1024)                  # fp32 or int16 CUDA tensor
     y = moving_average(x, grade=32, channels=2, algo="hillis")
+    y = moving_average_rows(x, grade=1024)             # [B, T] / [C, T] / [B, C, T]: every row on its own
 
 Semantics: ``basics/profilable_moving_averager.cpp:14-37`` -- interleaved
 frames, window ``grade`` frames, zero history (or ``history``: the
@@ -24,6 +25,10 @@ from ._lib import (ALGOS, F32, I16, MavgError, MavgLibraryError, algo_name,  # n
 __all__ = [
     "moving_average",
     "moving_average_into",
+    "moving_average_rows",
+    "moving_average_rows_into",
+    "rows_plan",
+    "rows_workspace_bytes",
     "fill_synthetic",
     "workspace_bytes",
     "resolve_algo",
@@ -172,6 +177,121 @@ def moving_average(x, grade: int, channels: int = 1, algo="auto", history=None,
         return out
     out = torch.empty_like(x)
     moving_average_into(x, out, grade, channels, algo, history, block_size, stream, library=library)
+    return out
+
+
+def rows_workspace_bytes(rows: int, row_frames: int, grade: int, channels: int = 1, dtype: int = F32,
+                         with_history: bool = False, library: Optional[str] = None) -> int:
+    """Device workspace ``moving_average_rows_into`` needs: 0 for the one-launch rows scan, the
+    single-row requirement for the per-row loop."""
+    import ctypes
+    out = ctypes.c_size_t(0)
+    _lib.check(_lib.load(library).mavg_rows_workspace_bytes(rows, row_frames, channels, grade, dtype,
+                                                            1 if with_history else 0, ctypes.byref(out)),
+               "mavg_rows_workspace_bytes")
+    return out.value
+
+
+def rows_plan(rows: int, row_frames: int, grade: int, channels: int = 1, dtype: int = F32,
+              with_history: bool = False, library: Optional[str] = None) -> str:
+    """What mavg_rows_run would do (nothing is launched): ``rows_scan<...> ... tile_frames=N ...``
+    (one launch of the segmented rows scan) or ``rows_loop rows=R x <one row's plan>`` (one
+    single-signal launch per row)."""
+    import ctypes
+    buf = ctypes.create_string_buffer(512)
+    _lib.check(_lib.load(library).mavg_rows_plan(rows, row_frames, channels, grade, dtype, 1 if with_history else 0,
+                                                 buf, len(buf)), "mavg_rows_plan")
+    return buf.value.decode()
+
+
+def _rows_shape(x, channels: int):
+    """(rows, row_frames) of a batch tensor: with one channel the last dimension is time and all
+    leading dimensions are rows ([C, T], [B, T], [B, C, T]); with ``channels`` > 1 the last
+    dimension is the channel and the one before it is time ([B, T, C])."""
+    if channels < 1:
+        raise ValueError(f"channels must be >= 1, got {channels}")
+    if channels == 1:
+        if x.dim() < 1:
+            raise ValueError("x must have a time dimension")
+        row_frames = x.shape[-1]
+    else:
+        if x.dim() < 2 or x.shape[-1] != channels:
+            raise ValueError(f"with channels={channels} x must be [..., time, {channels}], got {tuple(x.shape)}")
+        row_frames = x.shape[-2]
+    per_row = row_frames * channels
+    return (x.numel() // per_row if per_row else 0), row_frames
+
+
+def moving_average_rows_into(x, out, grade: int, channels: int = 1, history=None, stream=None, workspace=None,
+                             library: Optional[str] = None) -> None:
+    """Enqueue ``out = moving_average_rows(x)`` on ``stream`` (default: current).
+
+    ``x``: a contiguous device batch of independent signals (see ``moving_average_rows``).
+    ``history``: optional, ``rows * (grade-1) * channels`` samples, row r's history at
+    ``r * (grade-1) * channels``.  ``workspace``: as in ``moving_average_into``; only the per-row
+    loop needs one (``rows_workspace_bytes``), the one-launch rows scan needs none."""
+    torch = _torch()
+    if not (x.is_cuda and out.is_cuda):
+        raise ValueError("x and out must be device tensors (libmavg has no CPU path)")
+    if not (x.is_contiguous() and out.is_contiguous()):
+        raise ValueError("x and out must be contiguous")
+    if x.dtype != out.dtype or x.shape != out.shape:
+        raise ValueError("x and out must have the same dtype and shape")
+    dt = _dtype_code(x)
+    rows, row_frames = _rows_shape(x, channels)
+    hist_ptr = None
+    if history is not None:
+        if history.dtype != x.dtype or not history.is_cuda or not history.is_contiguous():
+            raise ValueError("history must be a contiguous device tensor of x's dtype")
+        if history.numel() != rows * (grade - 1) * channels:
+            raise ValueError(f"history must hold rows*(grade-1)*channels = {rows * (grade - 1) * channels} samples")
+        hist_ptr = history.data_ptr() if history.numel() else None
+    ws_n = rows_workspace_bytes(rows, row_frames, grade, channels, dt, hist_ptr is not None, library)
+    ws = None
+    if ws_n and workspace is not None:
+        if not (workspace.is_cuda and workspace.is_contiguous()):
+            raise ValueError("workspace must be a contiguous device tensor")
+        # (a workspace that is too small goes to the library: MAVG_ERR_WORKSPACE, nothing enqueued)
+        ws, ws_n = workspace, workspace.numel() * workspace.element_size()
+    elif ws_n:
+        if torch.cuda.is_current_stream_capturing():
+            raise ValueError(f"this batch runs the per-row loop, which needs a {ws_n}-byte workspace: "
+                             "inside a graph capture pass workspace= (see rows_workspace_bytes())")
+        # on the launch stream itself, as in moving_average_into
+        with torch.cuda.stream(stream) if stream is not None else _nullctx():
+            ws = torch.empty(ws_n, dtype=torch.uint8, device=x.device)
+    st = _lib.load(library).mavg_rows_run(x.data_ptr(), out.data_ptr(), rows, row_frames, channels, grade, dt,
+                                          hist_ptr, ws.data_ptr() if ws is not None else None, ws_n,
+                                          _stream_handle(stream, x.device))
+    _lib.check(st, "mavg_rows_run")
+
+
+def moving_average_rows(x, grade: int, channels: int = 1, history=None, stream=None, library: Optional[str] = None):
+    """Causal ``grade``-frame moving average of every row of a dense batch, each row filtered as
+    ``moving_average`` would filter it alone (zero history before its first frame, divisor
+    ``grade``), in one launch where the rows scan applies (``rows_plan``).
+
+    ``channels == 1``: the last dimension is time, all leading dimensions are rows -- planar audio
+    ``[C, T]``, batches ``[B, T]``, ``[B, C, T]``.  ``channels == C > 1``: ``[..., T, C]``,
+    interleaved frames.  The output has ``x``'s shape."""
+    torch = _torch()
+    _rows_shape(x, channels)
+    if not x.is_cuda:
+        raise ValueError("x must be a device tensor (libmavg has no CPU path)")
+    if not x.is_contiguous():
+        raise ValueError("x must be contiguous")
+    if stream is not None and stream != torch.cuda.current_stream(x.device):
+        # as moving_average: the launch stream waits for x's, `out` is allocated on it
+        stream.wait_stream(torch.cuda.current_stream(x.device))
+        with torch.cuda.stream(stream):
+            out = torch.empty_like(x)
+        moving_average_rows_into(x, out, grade, channels, history, stream, library=library)
+        x.record_stream(stream)
+        if history is not None:
+            history.record_stream(stream)
+        return out
+    out = torch.empty_like(x)
+    moving_average_rows_into(x, out, grade, channels, history, stream, library=library)
     return out
 
 

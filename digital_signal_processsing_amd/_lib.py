@@ -53,6 +53,9 @@ ERR_HIP = 5
 EXPORTED_SYMBOLS = (
     "mavg_workspace_bytes",
     "mavg_run",
+    "mavg_rows_run",
+    "mavg_rows_workspace_bytes",
+    "mavg_rows_plan",
     "mavg_resolve_algo",
     "mavg_plan",
     "mavg_fill_synthetic",
@@ -105,6 +108,12 @@ def load(path: str = None) -> ctypes.CDLL:
     lib.mavg_workspace_bytes.restype = i
     lib.mavg_run.argtypes = [vp, vp, sz, i, i, i, i, i, vp, vp, sz, vp]
     lib.mavg_run.restype = i
+    lib.mavg_rows_run.argtypes = [vp, vp, sz, sz, i, i, i, vp, vp, sz, vp]
+    lib.mavg_rows_run.restype = i
+    lib.mavg_rows_workspace_bytes.argtypes = [sz, sz, i, i, i, i, ctypes.POINTER(sz)]
+    lib.mavg_rows_workspace_bytes.restype = i
+    lib.mavg_rows_plan.argtypes = [sz, sz, i, i, i, i, ctypes.c_char_p, sz]
+    lib.mavg_rows_plan.restype = i
     lib.mavg_resolve_algo.argtypes = [sz, i, i, i, i]
     lib.mavg_resolve_algo.restype = i
     lib.mavg_plan.argtypes = [sz, i, i, i, i, i, ctypes.c_char_p, sz]

@@ -151,6 +151,131 @@ size_t plan_ws(size_t n, int C, int k, int dtype, int algo, int block) {
   return need;
 }
 
+// Alignment policy.  A vector algorithm (16-B or 8-B lane units) needs both
+// views unit-aligned.  When they are not:
+//   - same offset inside a unit, a whole number of frames: the first p < F
+//     frames (the "head") run in the frame-unit form of the same family, the
+//     rest (the "body") in the vector form; the body's history is the head
+//     itself (Sig::pre) followed, further back, by the caller's history;
+//   - otherwise the frame-unit form runs over the whole signal.
+// A frame-unit launch whose frames are not aligned to their own (vector)
+// size moves them as element accesses (Sig::eio).  Results are identical in
+// every case; only element alignment is required.
+//
+// mavg_run for one signal.  dry: every check mavg_run makes -- arguments, support, workspace --
+// with nothing enqueued (mavg_rows_run's loop plans every row before it launches any).
+int run_signal(const void* d_in, void* d_out, size_t n_samples, int channels, int grade, int dtype, int algo,
+               int block_size, const void* d_history, void* d_ws, size_t ws_bytes, void* stream, bool dry) {
+  const Workspace ws{d_ws, ws_bytes};
+  int st = validate(n_samples, channels, grade, dtype, algo, block_size);
+  if (st != MAVG_OK) return st;
+  if (n_samples == 0) return MAVG_OK;
+  if (d_in == nullptr || d_out == nullptr) return MAVG_ERR_INVALID_ARG;
+  const size_t eb = elem_size(dtype);
+  if (!aligned(d_in, eb) || !aligned(d_out, eb) || (d_history != nullptr && !aligned(d_history, eb)))
+    return MAVG_ERR_MISALIGNED;
+  algo = mavg_resolve_algo(n_samples, channels, grade, dtype, algo);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const int C = channels;
+  const size_t fb = eb * (size_t)C;
+  const long long nframes = (long long)(n_samples / (size_t)C);
+  // frame-unit launches: element IO when a frame is not aligned to its own vector size
+  auto frame_sig = [&](const void* in, void* out, const void* hist, long long nf, int pre) {
+    Sig sg{in, out, hist, nf, pre, 0};
+    const bool pow2 = (fb & (fb - 1)) == 0 && fb <= 32;
+    if (pow2 && (!aligned(in, fb) || !aligned(out, fb))) sg.eio = 1;
+    return sg;
+  };
+  // one launch in plan mode: its status and its workspace against the caller's
+  auto check = [&](int a, const Sig& sg) -> int {
+    LaunchPlan plan{};
+    g_plan = &plan;
+    const int c = launch_algo(a, dtype, C, sg, grade, block_size, nullptr, ws);
+    g_plan = nullptr;
+    if (c != MAVG_OK) return c;
+    if (plan.ws_bytes > 0 && (d_ws == nullptr || ws_bytes < plan.ws_bytes)) return MAVG_ERR_WORKSPACE;
+    if (plan.ws_bytes > 0 && !aligned(d_ws, 16)) return MAVG_ERR_MISALIGNED;
+    return MAVG_OK;
+  };
+  auto single = [&](int a, const Sig& sg) -> int {
+    return dry ? check(a, sg) : launch_algo(a, dtype, C, sg, grade, block_size, s, ws);
+  };
+  const int vu = vec_unit_bytes(algo, dtype, C);
+  if (vu == 0) return single(algo, frame_sig(d_in, d_out, d_history, nframes, 0));
+  if (aligned(d_in, vu) && aligned(d_out, vu)) return single(algo, Sig{d_in, d_out, d_history, nframes});
+  const size_t ai = reinterpret_cast<uintptr_t>(d_in) % (size_t)vu;
+  const size_t ao = reinterpret_cast<uintptr_t>(d_out) % (size_t)vu;
+  const int sf = scalar_form(algo);
+  if (ai != ao || ai % fb != 0) return single(sf, frame_sig(d_in, d_out, d_history, nframes, 0));
+  const long long p = std::min<long long>(nframes, (long long)(((size_t)vu - ai) / fb));
+  const Sig head = frame_sig(d_in, d_out, d_history, p, 0);
+  const size_t off = (size_t)p * fb;
+  const void* hist_body = d_history != nullptr ? static_cast<const char*>(d_history) + off : nullptr;
+  const Sig body{static_cast<const char*>(d_in) + off, static_cast<char*>(d_out) + off, hist_body, nframes - p,
+                 (int)p, 0};
+  // both launches are first made in plan mode: an error of the second one
+  // (e.g. a workspace that covers the head but not the body) must leave
+  // nothing on the stream (mavg.h)
+  for (int part = 0; part < (p == nframes ? 1 : 2); ++part) {
+    st = part == 0 ? check(sf, head) : check(algo, body);
+    if (st != MAVG_OK) return st;
+  }
+  if (dry) return MAVG_OK;
+  st = launch_algo(sf, dtype, C, head, grade, block_size, s, ws);
+  if (st != MAVG_OK || p == nframes) return st;
+  return launch_algo(algo, dtype, C, body, grade, block_size, s, ws);
+}
+
+// ---- rows (mavg_rows_run) -------------------------------------------------------------------
+// Arguments of the three rows entry points, as validate() does for mavg_run; *total = the
+// batch's frames.
+int validate_rows(size_t rows, size_t row_frames, int C, int k, int dtype, size_t* total) {
+  if (dtype != MAVG_I16 && dtype != MAVG_F32) return MAVG_ERR_INVALID_ARG;
+  if (C < 1 || k < 1) return MAVG_ERR_INVALID_ARG;
+  *total = 0;
+  if (rows == 0 || row_frames == 0) return MAVG_OK;
+  const size_t lim = (size_t)0x3fffffffffffffffULL;  // below 2^62 frames, as mavg_run
+  if (row_frames > lim / rows) return MAVG_ERR_UNSUPPORTED;
+  const size_t frames = rows * row_frames;
+  if (frames > (SIZE_MAX / 4) / (size_t)C) return MAVG_ERR_UNSUPPORTED;  // the byte count stays in size_t
+  *total = frames;
+  return MAVG_OK;
+}
+
+// The dispatch rule: the one-launch segmented scan for zero-history batches of one or two
+// channels whose effective halo fits its LDS stage (int16: sums in int32, grade <= 65535) and
+// whose rows are shorter than kRowsLoopRowBytes; everything else runs the single-signal dispatch
+// once per row ("rows_loop").
+// kRowsLoopRowBytes is the measured boundary (DESIGN.md "Rows", tools/bench_rows.py, 2^30
+// samples, k = 1024): a per-row loop of single-signal launches costs ~10 us a row on the host,
+// so it loses by 82x .. 32000x at rows of 128 KiB .. 1 KB, by 1.2x / 1.1x (fp32 / int16 stereo)
+// at rows of 32 MiB -- and ties (fp32, 0.99x) or wins (int16 stereo, 0.93x) at rows of 64 MiB,
+// where every row fills the device by itself and runs the single-signal tiles (0.78 - 0.82 of
+// peak against the rows scan's 0.59 - 0.67).
+constexpr size_t kRowsLoopRowBytes = (size_t)64 << 20;
+bool rows_fast_path(size_t row_frames, int C, int k, int dtype, bool with_history) {
+  if (with_history || C > 2) return false;
+  if (dtype == MAVG_I16 && k > 65535) return false;
+  if (k == 1) return true;  // the flat copy over the whole batch
+  if (row_frames >= kRowsLoopRowBytes / (elem_size(dtype) * (size_t)C)) return false;
+  return rows_scan_fits(dtype, C, row_frames, k);
+}
+
+// The fast path's one launch (plan mode when g_plan is set); views of any sample alignment.
+int rows_fast_launch(const void* in, void* out, size_t rows, size_t row_frames, size_t frames, int C, int k, int dtype,
+                     hipStream_t s) {
+  if (k == 1) return launch_identity(dtype, C, Sig{in, out, nullptr, (long long)frames}, s);
+  RowsSig rs{in, out, rows, row_frames};
+  const size_t fb = elem_size(dtype) * (size_t)C;
+  rs.unit = aligned(in, 16) && aligned(out, 16);
+  rs.eio = !rs.unit && (!aligned(in, fb) || !aligned(out, fb)) ? 1 : 0;
+  return rows_scan_any(dtype, C, rs, k, s);
+}
+
+// Rows whose alignment classes cover the batch's: row r's views sit r * row_bytes further, and
+// r * row_bytes mod 16 repeats after at most 16 rows.
+size_t rows_alignment_period(size_t rows) { return std::min<size_t>(rows, 16); }
+
 }  // namespace
 
 extern "C" {
@@ -213,69 +338,10 @@ int mavg_workspace_bytes(size_t n_samples, int channels, int grade, int dtype, i
   return MAVG_OK;
 }
 
-// Alignment policy.  A vector algorithm (16-B or 8-B lane units) needs both
-// views unit-aligned.  When they are not:
-//   - same offset inside a unit, a whole number of frames: the first p < F
-//     frames (the "head") run in the frame-unit form of the same family, the
-//     rest (the "body") in the vector form; the body's history is the head
-//     itself (Sig::pre) followed, further back, by the caller's history;
-//   - otherwise the frame-unit form runs over the whole signal.
-// A frame-unit launch whose frames are not aligned to their own (vector)
-// size moves them as element accesses (Sig::eio).  Results are identical in
-// every case; only element alignment is required.
 int mavg_run(const void* d_in, void* d_out, size_t n_samples, int channels, int grade, int dtype, int algo,
              int block_size, const void* d_history, void* d_ws, size_t ws_bytes, void* stream) {
-  const Workspace ws{d_ws, ws_bytes};
-  int st = validate(n_samples, channels, grade, dtype, algo, block_size);
-  if (st != MAVG_OK) return st;
-  if (n_samples == 0) return MAVG_OK;
-  if (d_in == nullptr || d_out == nullptr) return MAVG_ERR_INVALID_ARG;
-  const size_t eb = elem_size(dtype);
-  if (!aligned(d_in, eb) || !aligned(d_out, eb) || (d_history != nullptr && !aligned(d_history, eb)))
-    return MAVG_ERR_MISALIGNED;
-  algo = mavg_resolve_algo(n_samples, channels, grade, dtype, algo);
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  const int C = channels;
-  const size_t fb = eb * (size_t)C;
-  const long long nframes = (long long)(n_samples / (size_t)C);
-  // frame-unit launches: element IO when a frame is not aligned to its own vector size
-  auto frame_sig = [&](const void* in, void* out, const void* hist, long long nf, int pre) {
-    Sig sg{in, out, hist, nf, pre, 0};
-    const bool pow2 = (fb & (fb - 1)) == 0 && fb <= 32;
-    if (pow2 && (!aligned(in, fb) || !aligned(out, fb))) sg.eio = 1;
-    return sg;
-  };
-  const int vu = vec_unit_bytes(algo, dtype, C);
-  if (vu == 0) return launch_algo(algo, dtype, C, frame_sig(d_in, d_out, d_history, nframes, 0), grade, block_size, s, ws);
-  if (aligned(d_in, vu) && aligned(d_out, vu))
-    return launch_algo(algo, dtype, C, Sig{d_in, d_out, d_history, nframes}, grade, block_size, s, ws);
-  const size_t ai = reinterpret_cast<uintptr_t>(d_in) % (size_t)vu;
-  const size_t ao = reinterpret_cast<uintptr_t>(d_out) % (size_t)vu;
-  const int sf = scalar_form(algo);
-  if (ai != ao || ai % fb != 0)
-    return launch_algo(sf, dtype, C, frame_sig(d_in, d_out, d_history, nframes, 0), grade, block_size, s, ws);
-  const long long p = std::min<long long>(nframes, (long long)(((size_t)vu - ai) / fb));
-  const Sig head = frame_sig(d_in, d_out, d_history, p, 0);
-  const size_t off = (size_t)p * fb;
-  const void* hist_body = d_history != nullptr ? static_cast<const char*>(d_history) + off : nullptr;
-  const Sig body{static_cast<const char*>(d_in) + off, static_cast<char*>(d_out) + off, hist_body, nframes - p,
-                 (int)p, 0};
-  // both launches are first made in plan mode: an error of the second one
-  // (e.g. a workspace that covers the head but not the body) must leave
-  // nothing on the stream (mavg.h)
-  for (int part = 0; part < (p == nframes ? 1 : 2); ++part) {
-    LaunchPlan plan{};
-    g_plan = &plan;
-    st = part == 0 ? launch_algo(sf, dtype, C, head, grade, block_size, nullptr, ws)
-                   : launch_algo(algo, dtype, C, body, grade, block_size, nullptr, ws);
-    g_plan = nullptr;
-    if (st != MAVG_OK) return st;
-    if (plan.ws_bytes > 0 && (d_ws == nullptr || ws_bytes < plan.ws_bytes)) return MAVG_ERR_WORKSPACE;
-    if (plan.ws_bytes > 0 && !aligned(d_ws, 16)) return MAVG_ERR_MISALIGNED;
-  }
-  st = launch_algo(sf, dtype, C, head, grade, block_size, s, ws);
-  if (st != MAVG_OK || p == nframes) return st;
-  return launch_algo(algo, dtype, C, body, grade, block_size, s, ws);
+  return run_signal(d_in, d_out, n_samples, channels, grade, dtype, algo, block_size, d_history, d_ws, ws_bytes, stream,
+                    false);
 }
 
 int mavg_plan(size_t n_samples, int channels, int grade, int dtype, int algo, int block_size, char* buf,
@@ -323,6 +389,100 @@ int mavg_stream_copy(const void* d_in, void* d_out, size_t bytes, void* stream) 
   if (d_in == nullptr || d_out == nullptr || bytes % 16 != 0) return MAVG_ERR_INVALID_ARG;
   if (!aligned(d_in, 16) || !aligned(d_out, 16)) return MAVG_ERR_MISALIGNED;
   return launch_flat_copy(d_in, d_out, bytes, static_cast<hipStream_t>(stream));
+}
+
+int mavg_rows_workspace_bytes(size_t rows, size_t row_frames, int channels, int grade, int dtype, int with_history,
+                              size_t* out_bytes) {
+  if (out_bytes == nullptr) return MAVG_ERR_INVALID_ARG;
+  size_t frames = 0;
+  const int st = validate_rows(rows, row_frames, channels, grade, dtype, &frames);
+  if (st != MAVG_OK) return st;
+  *out_bytes = 0;
+  if (frames == 0) return MAVG_OK;
+  if (rows_fast_path(row_frames, channels, grade, dtype, with_history != 0)) {
+    // no workspace; the launch's own limit (grid_too_large) shows here as it does in mavg_rows_run
+    LaunchPlan plan{};
+    g_plan = &plan;
+    const int c = rows_fast_launch(reinterpret_cast<const void*>(uintptr_t(1) << 20),
+                                   reinterpret_cast<void*>(uintptr_t(1) << 21), rows, row_frames, frames, channels,
+                                   grade, dtype, nullptr);
+    g_plan = nullptr;
+    return c;
+  }
+  return mavg_workspace_bytes(row_frames * (size_t)channels, channels, grade, dtype, MAVG_ALGO_AUTO, 0, out_bytes);
+}
+
+int mavg_rows_plan(size_t rows, size_t row_frames, int channels, int grade, int dtype, int with_history, char* buf,
+                   size_t buflen) {
+  if (buf == nullptr || buflen == 0) return MAVG_ERR_INVALID_ARG;
+  buf[0] = 0;
+  if (rows == 0 || row_frames == 0) return MAVG_ERR_INVALID_ARG;
+  size_t frames = 0;
+  const int st = validate_rows(rows, row_frames, channels, grade, dtype, &frames);
+  if (st != MAVG_OK) return st;
+  if (rows_fast_path(row_frames, channels, grade, dtype, with_history != 0)) {
+    LaunchPlan plan{};
+    g_plan = &plan;
+    // 16-B-aligned dummy device pointers: nothing is launched or dereferenced in plan mode
+    const int c = rows_fast_launch(reinterpret_cast<const void*>(uintptr_t(1) << 20),
+                                   reinterpret_cast<void*>(uintptr_t(1) << 21), rows, row_frames, frames, channels,
+                                   grade, dtype, nullptr);
+    g_plan = nullptr;
+    if (c != MAVG_OK) return c;
+    if (grade == 1)  // the flat copy over the whole batch
+      snprintf(buf, buflen, "rows_scan<%s,C=%d,k=1> rows=%zu row_frames=%zu: %s", dtype == MAVG_F32 ? "f32" : "i16",
+               channels, rows, row_frames, plan.text);
+    else
+      snprintf(buf, buflen, "%s", plan.text);
+    return MAVG_OK;
+  }
+  char row[sizeof(LaunchPlan::text)];
+  const int c = mavg_plan(row_frames * (size_t)channels, channels, grade, dtype, MAVG_ALGO_AUTO, 0, row, sizeof(row));
+  if (c != MAVG_OK) return c;
+  snprintf(buf, buflen, "rows_loop rows=%zu x %s", rows, row);
+  return MAVG_OK;
+}
+
+// One launch of the segmented rows scan where it applies (rows_fast_path), else the single-signal
+// dispatch once per row on the same stream, every row planned before the first is launched.
+int mavg_rows_run(const void* d_in, void* d_out, size_t rows, size_t row_frames, int channels, int grade, int dtype,
+                  const void* d_history, void* d_ws, size_t ws_bytes, void* stream) {
+  size_t frames = 0;
+  const int st = validate_rows(rows, row_frames, channels, grade, dtype, &frames);
+  if (st != MAVG_OK) return st;
+  if (frames == 0) return MAVG_OK;
+  if (d_in == nullptr || d_out == nullptr) return MAVG_ERR_INVALID_ARG;
+  const size_t eb = elem_size(dtype);
+  if (!aligned(d_in, eb) || !aligned(d_out, eb) || (d_history != nullptr && !aligned(d_history, eb)))
+    return MAVG_ERR_MISALIGNED;
+  if (rows_fast_path(row_frames, channels, grade, dtype, d_history != nullptr))
+    return rows_fast_launch(d_in, d_out, rows, row_frames, frames, channels, grade, dtype,
+                            static_cast<hipStream_t>(stream));
+  // rows_loop: `rows` launches (a misaligned row: two), all sharing the caller's workspace --
+  // launches on one stream are serial and each zeroes its records
+  const size_t row_samples = row_frames * (size_t)channels;
+  const size_t row_bytes = row_samples * eb;
+  const size_t hist_bytes = (size_t)(grade - 1) * (size_t)channels * eb;
+  auto row_run = [&](size_t r, bool dry) -> int {
+    const void* h = d_history != nullptr ? static_cast<const char*>(d_history) + r * hist_bytes : nullptr;
+    return run_signal(static_cast<const char*>(d_in) + r * row_bytes, static_cast<char*>(d_out) + r * row_bytes,
+                      row_samples, channels, grade, dtype, MAVG_ALGO_AUTO, 0, h, d_ws, ws_bytes, stream, dry);
+  };
+  // the workspace contract is mavg_rows_workspace_bytes' (whatever the rows' alignment), not
+  // only what these rows' forms happen to need
+  const size_t need = plan_ws(row_samples, channels, grade, dtype,
+                              mavg_resolve_algo(row_samples, channels, grade, dtype, MAVG_ALGO_AUTO), 0);
+  if (need > 0 && (d_ws == nullptr || ws_bytes < need)) return MAVG_ERR_WORKSPACE;
+  if (need > 0 && !aligned(d_ws, 16)) return MAVG_ERR_MISALIGNED;
+  for (size_t r = 0; r < rows_alignment_period(rows); ++r) {
+    const int c = row_run(r, true);
+    if (c != MAVG_OK) return c;
+  }
+  for (size_t r = 0; r < rows; ++r) {
+    const int c = row_run(r, false);
+    if (c != MAVG_OK) return c;
+  }
+  return MAVG_OK;
 }
 
 }  // extern "C"

@@ -120,6 +120,34 @@ __device__ __forceinline__ void wave_incl_scan_n(A (&v)[N]) {
   for (int i = 0; i < N; ++i) v[i] += dpp<0x143, 0xc, 0xf>(v[i]);
 }
 
+// Segmented inclusive scan across the 64 lanes (mavg_rows.hpp): N values per lane that share one
+// flag, "a segment starts in this lane".  The operator on (flag, value) pairs is
+//     (fa, a) (+) (fb, b) = (fa | fb, fb ? b : a + b)
+// -- associative, so the six steps of wave_incl_scan apply unchanged: at each step a lane adds the
+// incoming value only while it has seen no segment start, then ORs the flags.  A select, never a
+// multiply by the flag: what lies before a segment start (another row's Inf, NaN or magnitude)
+// must not reach the sums after it, not even as a term that would cancel.  Lanes a step does not
+// write receive (0, 0), the operator's identity.
+template <int CTRL, int RM, typename A, int N>
+__device__ __forceinline__ void seg_scan_step(int32_t& f, A (&v)[N]) {
+  const int32_t fi = dpp<CTRL, RM, 0xf>(f);
+#pragma unroll
+  for (int i = 0; i < N; ++i) {
+    const A vi = dpp<CTRL, RM, 0xf>(v[i]);
+    v[i] = f != 0 ? v[i] : v[i] + vi;
+  }
+  f |= fi;
+}
+template <typename A, int N>
+__device__ __forceinline__ void wave_seg_incl_scan(int32_t& f, A (&v)[N]) {
+  seg_scan_step<0x111, 0xf>(f, v);
+  seg_scan_step<0x112, 0xf>(f, v);
+  seg_scan_step<0x114, 0xf>(f, v);
+  seg_scan_step<0x118, 0xf>(f, v);
+  seg_scan_step<0x142, 0xa>(f, v);
+  seg_scan_step<0x143, 0xc>(f, v);
+}
+
 __device__ __forceinline__ int32_t readlane(int32_t v, int l) { return __builtin_amdgcn_readlane(v, l); }
 __device__ __forceinline__ double readlane(double v, int l) {
   return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), l),

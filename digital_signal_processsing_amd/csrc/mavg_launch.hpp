@@ -114,6 +114,25 @@ int scan_i16_wide(int C, bool vec, bool hs, const Sig& sg, int k, int block, hip
 int direct_any(int dtype, bool wide, int C, int width, const Sig& sg, int k, int block, hipStream_t st);
 int naive_any(int dtype, bool wide, const Sig& sg, int C, int k, int block, hipStream_t st);
 
+// The batched rows scan (mavg_rows.hpp, instantiated in mavg_rows.hip): `rows` signals of
+// `row_frames` frames each, dense, zero history, C = 1 or 2, one launch.
+//   unit  the 16-B-unit form (both views 16-B aligned); else the frame-unit (F = 1) form
+//   eio   frame-unit form on views that are only element-aligned (UnitIO::gload)
+struct RowsSig {
+  const void* in;
+  void* out;
+  size_t rows;
+  size_t row_frames;
+  bool unit = true;
+  int eio = 0;
+};
+// Whether the effective halo of min(grade, row_frames) frames fits the LDS stage of the rows
+// kernel in both of its forms (the dispatch rule of mavg_rows_run; the same lds_budget check
+// launch_tile_scan makes).
+bool rows_scan_fits(int dtype, int C, size_t row_frames, int grade);
+// MAVG_ERR_UNSUPPORTED: the halo does not fit, or the launch would exceed grid_too_large
+int rows_scan_any(int dtype, int C, const RowsSig& rs, int grade, hipStream_t st);
+
 // flat-tile scan: one workgroup per tile, carry rebuilt from the k-frame halo
 // DV: the int16 output division of the tile scan -- the magic multiply, which
 // measured faster than the fp64 product here (int16 stereo k=1024: 0.779 vs

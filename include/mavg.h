@@ -139,6 +139,68 @@ int mavg_run(const void* d_in, void* d_out, size_t n_samples, int channels,
              int grade, int dtype, int algo, int block_size,
              const void* d_history, void* d_ws, size_t ws_bytes, void* stream);
 
+/*
+ * Batched rows: `rows` independent signals of `row_frames` frames each,
+ * stored densely one after another (no row stride: row r starts at sample
+ * r * row_frames * channels), every one filtered exactly as mavg_run would
+ * filter it alone -- zero history before the row's frame 0 (or the row's own
+ * history), divisor `grade` also in the warm-up and when grade > row_frames,
+ * the same int16 / fp32 arithmetic.  A row's outputs depend on that row's
+ * samples (and its history) only: nothing of another row enters them, not even
+ * as a term that cancels (a neighbour's Inf or NaN stays in the neighbour).
+ *   d_in/d_out any sample-aligned views of rows * row_frames * channels samples.
+ *   d_history  NULL, or rows * (grade-1) * channels samples: row r's history
+ *              at sample r * (grade-1) * channels.
+ *   d_ws       mavg_rows_workspace_bytes() bytes, 16-B aligned (NULL when 0).
+ * Ownership, stream and capture rules are mavg_run's: no allocation, no
+ * synchronisation, nothing enqueued unless MAVG_OK is returned (MAVG_ERR_HIP
+ * excepted).  rows == 0 or row_frames == 0: MAVG_OK, nothing enqueued.
+ *
+ * Dispatch (mavg_rows_plan shows which):
+ *   rows_scan  ONE launch of the segmented rows scan over the whole batch, no
+ *              workspace: d_history == NULL, channels 1 or 2, int16 grade <=
+ *              65535, and the effective halo of min(grade, row_frames) frames
+ *              is at most 16 KiB (min(grade, row_frames) * channels <= 4096
+ *              fp32 or 8192 int16 samples: the LDS-staged halos, as far as
+ *              mavg_run's own tiles go), and rows shorter than 64 MiB.  Tiles ignore row
+ *              boundaries: rows of 5 frames and of 2^24 frames run the same
+ *              code at the same rate.  Views that are not both 16-B aligned
+ *              run its one-frame-per-lane form.  grade == 1 is the flat copy.
+ *   rows_loop  everything else (a history, channels >= 3, windows and rows
+ *              both past 16 KiB of halo, int16 grade > 65535, and rows of
+ *              64 MiB or more, which fill the device one at a time and measured
+ *              no slower that way, DESIGN.md "Rows"): mavg_run's
+ *              dispatch (MAVG_ALGO_AUTO, block_size 0) once per row on
+ *              `stream` -- it costs `rows` launches (twice that for rows whose
+ *              views it peels), correct but not fast.  All rows share d_ws.
+ *              Every row is planned before the first is launched: a workspace
+ *              or support error leaves the stream untouched.
+ *
+ * Supported maximum.  rows * row_frames < 2^62 frames (and the byte count in
+ * size_t), else MAVG_ERR_UNSUPPORTED.  rows_scan makes one launch of `block`
+ * threads per `tile_frames` frames (both in mavg_rows_plan's text), so it takes
+ *     rows * row_frames <= (2^32 - 1) / block * tile_frames
+ * frames: 2^35 (fp32 mono) and more in the 16-B-unit form, 2^34 frames in the
+ * one-frame-per-lane form of views off 16-B alignment; past it
+ * MAVG_ERR_UNSUPPORTED, nothing enqueued.  rows_loop: each row is a mavg_run
+ * signal (the "Supported maximum" above).  Tested on a 2^31 + 2^16-sample
+ * int16 batch (tests/test_gpu_rows.py).
+ */
+int mavg_rows_run(const void* d_in, void* d_out, size_t rows, size_t row_frames,
+                  int channels, int grade, int dtype, const void* d_history,
+                  void* d_ws, size_t ws_bytes, void* stream);
+
+/* Device workspace (bytes) mavg_rows_run needs: 0 for rows_scan; for
+ * rows_loop what mavg_workspace_bytes gives for one row (the rows share it). */
+int mavg_rows_workspace_bytes(size_t rows, size_t row_frames, int channels, int grade,
+                              int dtype, int with_history, size_t* out_bytes);
+
+/* Describe, without launching anything, what mavg_rows_run would do on
+ * 16-B-aligned views: "rows_scan<...> ... tile_frames=N ..." or
+ * "rows_loop rows=R x <mavg_plan's text for one row>" (up to ~300 characters). */
+int mavg_rows_plan(size_t rows, size_t row_frames, int channels, int grade, int dtype,
+                   int with_history, char* buf, size_t buflen);
+
 /* Describe, without launching anything, the kernel and launch geometry
  * mavg_run would use for these arguments on 16-B-aligned views
  * (e.g. "tile_scan<f32,...> grid=... block=256 ..."). */
