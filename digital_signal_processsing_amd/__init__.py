@@ -8,6 +8,7 @@ only for device memory and streams.
     y = moving_average(x, grade=1024)                  # fp32 or int16 CUDA tensor
     y = moving_average(x, grade=32, channels=2, algo="hillis")
     y = moving_average_rows(x, grade=1024)             # [B, T] / [C, T] / [B, C, T]: every row on its own
+    y = moving_average_ragged(x, grade=1024, lengths=[5, 0, 30011, 7])   # packed rows of different lengths
 
 Semantics: ``basics/profilable_moving_averager.cpp:14-37`` -- interleaved
 frames, window ``grade`` frames, zero history (or ``history``: the
@@ -29,6 +30,10 @@ __all__ = [
     "moving_average_rows_into",
     "rows_plan",
     "rows_workspace_bytes",
+    "moving_average_ragged",
+    "moving_average_ragged_into",
+    "ragged_plan",
+    "ragged_workspace_bytes",
     "fill_synthetic",
     "workspace_bytes",
     "resolve_algo",
@@ -292,6 +297,170 @@ def moving_average_rows(x, grade: int, channels: int = 1, history=None, stream=N
         return out
     out = torch.empty_like(x)
     moving_average_rows_into(x, out, grade, channels, history, stream, library=library)
+    return out
+
+
+def _host_offsets(offsets, lengths):
+    """The rows + 1 frame offsets as a contiguous host int64 tensor, from exactly one of
+    ``offsets`` (rows + 1 entries) or ``lengths`` (rows entries, cumulated here); either a host
+    int64 tensor, a sequence or a numpy array."""
+    torch = _torch()
+    if (offsets is None) == (lengths is None):
+        raise ValueError("give exactly one of offsets= and lengths=")
+    given = offsets if offsets is not None else lengths
+    what = "offsets" if offsets is not None else "lengths"
+    if isinstance(given, torch.Tensor) and given.is_cuda:
+        raise ValueError(f"{what} must be in host memory (the device copy goes in offsets_device=)")
+    try:
+        t = torch.as_tensor(given)
+    except (TypeError, ValueError, RuntimeError) as e:
+        raise ValueError(f"{what} must be a host int64 tensor, a sequence or a numpy array of integers: {e}") from None
+    if t.numel() and (t.is_floating_point() or t.is_complex() or t.dtype == torch.bool):
+        raise ValueError(f"{what} must be integers, got {t.dtype}")
+    t = t.to(torch.int64)
+    if t.dim() != 1:
+        raise ValueError(f"{what} must be one-dimensional, got shape {tuple(t.shape)}")
+    if lengths is not None:
+        if t.numel() and int(t.min()) < 0:
+            raise ValueError("lengths must be >= 0")
+        off = torch.zeros(t.numel() + 1, dtype=torch.int64)
+        torch.cumsum(t, 0, out=off[1:])
+        return off
+    if t.numel() < 1:
+        raise ValueError("offsets must hold rows + 1 entries (at least the leading 0)")
+    if int(t[0]) != 0:
+        raise ValueError(f"offsets must start at 0, got {int(t[0])}")
+    if t.numel() > 1 and bool((t[1:] < t[:-1]).any()):
+        raise ValueError("offsets must be non-decreasing")
+    return t.contiguous()
+
+
+def _offsets_ptr(off):
+    import ctypes
+    return ctypes.cast(off.data_ptr(), ctypes.POINTER(ctypes.c_int64))
+
+
+def ragged_workspace_bytes(offsets, grade: int, channels: int = 1, dtype: int = F32,
+                           library: Optional[str] = None) -> int:
+    """Device workspace ``moving_average_ragged_into`` needs: 0 for the one-launch ragged scan,
+    the longest row's single-signal requirement for the per-row loop."""
+    import ctypes
+    off = _host_offsets(offsets, None)
+    out = ctypes.c_size_t(0)
+    _lib.check(_lib.load(library).mavg_ragged_workspace_bytes(_offsets_ptr(off), off.numel() - 1, channels, grade,
+                                                              dtype, ctypes.byref(out)), "mavg_ragged_workspace_bytes")
+    return out.value
+
+
+def ragged_plan(offsets, grade: int, channels: int = 1, dtype: int = F32, library: Optional[str] = None) -> str:
+    """What mavg_ragged_run would do (nothing is launched): ``ragged_scan<...> rows=R frames=N
+    max_row_frames=M window=min(grade,M) ... tile_frames=T ...`` (one launch of the ragged scan) or
+    ``ragged_loop rows=R max_row_frames=M x <the longest row's plan>`` (one single-signal launch
+    per non-empty row)."""
+    import ctypes
+    off = _host_offsets(offsets, None)
+    buf = ctypes.create_string_buffer(512)
+    _lib.check(_lib.load(library).mavg_ragged_plan(_offsets_ptr(off), off.numel() - 1, channels, grade, dtype,
+                                                   buf, len(buf)), "mavg_ragged_plan")
+    return buf.value.decode()
+
+
+def _ragged_frames(x, channels: int) -> int:
+    """Frames of a packed ragged batch: ``[frames]`` with one channel, ``[frames, C]`` interleaved."""
+    if channels < 1:
+        raise ValueError(f"channels must be >= 1, got {channels}")
+    if channels == 1:
+        if x.dim() != 1:
+            raise ValueError(f"with channels=1 x must be the packed stream [frames], got {tuple(x.shape)}")
+    elif x.dim() != 2 or x.shape[-1] != channels:
+        raise ValueError(f"with channels={channels} x must be [frames, {channels}], got {tuple(x.shape)}")
+    return x.shape[0]
+
+
+def moving_average_ragged_into(x, out, grade: int, offsets=None, lengths=None, channels: int = 1,
+                               offsets_device=None, stream=None, workspace=None,
+                               library: Optional[str] = None) -> None:
+    """Enqueue ``out = moving_average_ragged(x)`` on ``stream`` (default: current).
+
+    ``x``: the packed device tensor, ``[frames]`` (one channel) or ``[frames, C]`` interleaved;
+    row r is frames ``offsets[r] .. offsets[r+1]``.  Exactly one of ``offsets`` (rows + 1 entries,
+    starting at 0, non-decreasing, ending at x's frame count) or ``lengths`` (rows entries,
+    cumulated on the host): a host int64 tensor, a sequence or a numpy array.
+    ``offsets_device``: optional int64 device tensor holding the same rows + 1 offsets (what the
+    kernel reads); without it the offsets are uploaded on the launch stream, which a graph
+    capture cannot do -- pass it there.  ``workspace``: as in ``moving_average_rows_into``; only
+    the per-row loop needs one (``ragged_workspace_bytes``)."""
+    torch = _torch()
+    if not (x.is_cuda and out.is_cuda):
+        raise ValueError("x and out must be device tensors (libmavg has no CPU path)")
+    if not (x.is_contiguous() and out.is_contiguous()):
+        raise ValueError("x and out must be contiguous")
+    if x.dtype != out.dtype or x.shape != out.shape:
+        raise ValueError("x and out must have the same dtype and shape")
+    dt = _dtype_code(x)
+    frames = _ragged_frames(x, channels)
+    off = _host_offsets(offsets, lengths)
+    rows = off.numel() - 1
+    if int(off[-1]) != frames:
+        raise ValueError(f"the offsets end at {int(off[-1])} frames, x holds {frames}")
+    if offsets_device is not None:
+        if not (offsets_device.is_cuda and offsets_device.is_contiguous() and offsets_device.dtype == torch.int64):
+            raise ValueError("offsets_device must be a contiguous int64 device tensor")
+        if offsets_device.numel() != rows + 1:
+            raise ValueError(f"offsets_device must hold rows + 1 = {rows + 1} entries, got {offsets_device.numel()}")
+    ws_n = ragged_workspace_bytes(off, grade, channels, dt, library)
+    if rows == 0 or frames == 0:
+        return  # validated above and by the library's workspace query; nothing to enqueue
+    if offsets_device is None:
+        if torch.cuda.is_current_stream_capturing():
+            raise ValueError("the offsets would be uploaded to the device here: inside a graph capture pass "
+                             "offsets_device= (an int64 device tensor of the rows + 1 offsets)")
+        # on the launch stream itself (a copy from pageable host memory returns when it is staged)
+        with torch.cuda.stream(stream) if stream is not None else _nullctx():
+            offsets_device = off.to(x.device)
+    ws = None
+    if ws_n and workspace is not None:
+        if not (workspace.is_cuda and workspace.is_contiguous()):
+            raise ValueError("workspace must be a contiguous device tensor")
+        # (a workspace that is too small goes to the library: MAVG_ERR_WORKSPACE, nothing enqueued)
+        ws, ws_n = workspace, workspace.numel() * workspace.element_size()
+    elif ws_n:
+        if torch.cuda.is_current_stream_capturing():
+            raise ValueError(f"this batch runs the per-row loop, which needs a {ws_n}-byte workspace: "
+                             "inside a graph capture pass workspace= (see ragged_workspace_bytes())")
+        with torch.cuda.stream(stream) if stream is not None else _nullctx():
+            ws = torch.empty(ws_n, dtype=torch.uint8, device=x.device)
+    st = _lib.load(library).mavg_ragged_run(x.data_ptr(), out.data_ptr(), _offsets_ptr(off),
+                                            offsets_device.data_ptr(), rows, channels, grade, dt,
+                                            ws.data_ptr() if ws is not None else None, ws_n,
+                                            _stream_handle(stream, x.device))
+    _lib.check(st, "mavg_ragged_run")
+    if stream is not None:
+        offsets_device.record_stream(stream)
+
+
+def moving_average_ragged(x, grade: int, offsets=None, lengths=None, channels: int = 1, offsets_device=None,
+                          stream=None, library: Optional[str] = None):
+    """Causal ``grade``-frame moving average of every row of a packed ragged batch, each row
+    filtered as ``moving_average`` would filter it alone (zero history before its first frame,
+    divisor ``grade``), in one launch where the ragged scan applies (``ragged_plan``).  Arguments
+    as ``moving_average_ragged_into``; the output has ``x``'s shape."""
+    torch = _torch()
+    _ragged_frames(x, channels)
+    if not x.is_cuda:
+        raise ValueError("x must be a device tensor (libmavg has no CPU path)")
+    if not x.is_contiguous():
+        raise ValueError("x must be contiguous")
+    if stream is not None and stream != torch.cuda.current_stream(x.device):
+        # as moving_average: the launch stream waits for x's, `out` is allocated on it
+        stream.wait_stream(torch.cuda.current_stream(x.device))
+        with torch.cuda.stream(stream):
+            out = torch.empty_like(x)
+        moving_average_ragged_into(x, out, grade, offsets, lengths, channels, offsets_device, stream, library=library)
+        x.record_stream(stream)
+        return out
+    out = torch.empty_like(x)
+    moving_average_ragged_into(x, out, grade, offsets, lengths, channels, offsets_device, stream, library=library)
     return out
 
 

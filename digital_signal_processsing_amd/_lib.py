@@ -56,6 +56,9 @@ EXPORTED_SYMBOLS = (
     "mavg_rows_run",
     "mavg_rows_workspace_bytes",
     "mavg_rows_plan",
+    "mavg_ragged_run",
+    "mavg_ragged_workspace_bytes",
+    "mavg_ragged_plan",
     "mavg_resolve_algo",
     "mavg_plan",
     "mavg_fill_synthetic",
@@ -114,6 +117,13 @@ def load(path: str = None) -> ctypes.CDLL:
     lib.mavg_rows_workspace_bytes.restype = i
     lib.mavg_rows_plan.argtypes = [sz, sz, i, i, i, i, ctypes.c_char_p, sz]
     lib.mavg_rows_plan.restype = i
+    i64p = ctypes.POINTER(ctypes.c_int64)  # host offsets; the device copy is an address (vp)
+    lib.mavg_ragged_run.argtypes = [vp, vp, i64p, vp, sz, i, i, i, vp, sz, vp]
+    lib.mavg_ragged_run.restype = i
+    lib.mavg_ragged_workspace_bytes.argtypes = [i64p, sz, i, i, i, ctypes.POINTER(sz)]
+    lib.mavg_ragged_workspace_bytes.restype = i
+    lib.mavg_ragged_plan.argtypes = [i64p, sz, i, i, i, ctypes.c_char_p, sz]
+    lib.mavg_ragged_plan.restype = i
     lib.mavg_resolve_algo.argtypes = [sz, i, i, i, i]
     lib.mavg_resolve_algo.restype = i
     lib.mavg_plan.argtypes = [sz, i, i, i, i, i, ctypes.c_char_p, sz]

@@ -276,6 +276,58 @@ int rows_fast_launch(const void* in, void* out, size_t rows, size_t row_frames, 
 // r * row_bytes mod 16 repeats after at most 16 rows.
 size_t rows_alignment_period(size_t rows) { return std::min<size_t>(rows, 16); }
 
+// ---- ragged rows (mavg_ragged_run) ----------------------------------------------------------
+// Arguments of the three ragged entry points and the host offsets: *total = off[rows], *longest =
+// the longest row, both in frames (0 for an empty batch).
+int validate_ragged(const int64_t* off, size_t rows, int C, int k, int dtype, size_t* total, size_t* longest) {
+  if (dtype != MAVG_I16 && dtype != MAVG_F32) return MAVG_ERR_INVALID_ARG;
+  if (C < 1 || k < 1) return MAVG_ERR_INVALID_ARG;
+  *total = 0;
+  *longest = 0;
+  if (rows == 0) return MAVG_OK;
+  if (off == nullptr || off[0] != 0) return MAVG_ERR_INVALID_ARG;
+  if (rows > (size_t)0x3fffffffffffffffULL) return MAVG_ERR_UNSUPPORTED;  // row indices stay in int64
+  int64_t longest_row = 0;
+  for (size_t r = 0; r < rows; ++r) {
+    if (off[r + 1] < off[r]) return MAVG_ERR_INVALID_ARG;
+    longest_row = std::max(longest_row, off[r + 1] - off[r]);
+  }
+  const size_t frames = (size_t)off[rows];
+  if (frames > (size_t)0x3fffffffffffffffULL) return MAVG_ERR_UNSUPPORTED;  // below 2^62 frames, as mavg_run
+  if (frames > (SIZE_MAX / 4) / (size_t)C) return MAVG_ERR_UNSUPPORTED;     // the byte count stays in size_t
+  *total = frames;
+  *longest = (size_t)longest_row;
+  return MAVG_OK;
+}
+
+// The dispatch rule: the one-launch ragged scan for batches of one or two channels whose
+// effective halo min(grade, longest row) fits its LDS (int16: sums in int32, grade <= 65535);
+// everything else runs the single-signal dispatch once per non-empty row ("ragged_loop").  The
+// rows scan's 64-MiB-row rule is NOT carried over: it was measured on uniform batches, and a
+// batch with one huge row among small ones has not been measured (DESIGN.md "Ragged").
+bool ragged_fast_path(size_t longest, int C, int k, int dtype) {
+  if (C > 2) return false;
+  if (dtype == MAVG_I16 && k > 65535) return false;
+  if (k == 1) return true;  // the flat copy over the packed stream
+  return ragged_scan_fits(dtype, C, longest, k);
+}
+
+// The fast path's one launch (plan mode when g_plan is set); views of any sample alignment.
+int ragged_fast_launch(const void* in, void* out, const void* d_off, size_t rows, size_t frames, size_t longest, int C,
+                       int k, int dtype, hipStream_t s) {
+  if (k == 1) return launch_identity(dtype, C, Sig{in, out, nullptr, (long long)frames}, s);
+  RaggedSig rs{in, out, d_off, rows, frames, longest};
+  const size_t fb = elem_size(dtype) * (size_t)C;
+  rs.unit = aligned(in, 16) && aligned(out, 16);
+  rs.eio = !rs.unit && (!aligned(in, fb) || !aligned(out, fb)) ? 1 : 0;
+  return ragged_scan_any(dtype, C, rs, k, s);
+}
+
+// 16-B-aligned dummy device pointers for plan mode: nothing is launched or dereferenced
+const void* const kPlanIn = reinterpret_cast<const void*>(uintptr_t(1) << 20);
+void* const kPlanOut = reinterpret_cast<void*>(uintptr_t(1) << 21);
+const void* const kPlanOff = reinterpret_cast<const void*>(uintptr_t(1) << 22);
+
 }  // namespace
 
 extern "C" {
@@ -475,6 +527,96 @@ int mavg_rows_run(const void* d_in, void* d_out, size_t rows, size_t row_frames,
   if (need > 0 && (d_ws == nullptr || ws_bytes < need)) return MAVG_ERR_WORKSPACE;
   if (need > 0 && !aligned(d_ws, 16)) return MAVG_ERR_MISALIGNED;
   for (size_t r = 0; r < rows_alignment_period(rows); ++r) {
+    const int c = row_run(r, true);
+    if (c != MAVG_OK) return c;
+  }
+  for (size_t r = 0; r < rows; ++r) {
+    const int c = row_run(r, false);
+    if (c != MAVG_OK) return c;
+  }
+  return MAVG_OK;
+}
+
+int mavg_ragged_workspace_bytes(const int64_t* h_offsets, size_t rows, int channels, int grade, int dtype,
+                                size_t* out_bytes) {
+  if (out_bytes == nullptr) return MAVG_ERR_INVALID_ARG;
+  size_t frames = 0, longest = 0;
+  const int st = validate_ragged(h_offsets, rows, channels, grade, dtype, &frames, &longest);
+  if (st != MAVG_OK) return st;
+  *out_bytes = 0;
+  if (frames == 0) return MAVG_OK;
+  if (ragged_fast_path(longest, channels, grade, dtype)) {
+    // no workspace; the launch's own limit (grid_too_large) shows here as it does in mavg_ragged_run
+    LaunchPlan plan{};
+    g_plan = &plan;
+    const int c = ragged_fast_launch(kPlanIn, kPlanOut, kPlanOff, rows, frames, longest, channels, grade, dtype, nullptr);
+    g_plan = nullptr;
+    return c;
+  }
+  return mavg_workspace_bytes(longest * (size_t)channels, channels, grade, dtype, MAVG_ALGO_AUTO, 0, out_bytes);
+}
+
+int mavg_ragged_plan(const int64_t* h_offsets, size_t rows, int channels, int grade, int dtype, char* buf,
+                     size_t buflen) {
+  if (buf == nullptr || buflen == 0) return MAVG_ERR_INVALID_ARG;
+  buf[0] = 0;
+  size_t frames = 0, longest = 0;
+  const int st = validate_ragged(h_offsets, rows, channels, grade, dtype, &frames, &longest);
+  if (st != MAVG_OK) return st;
+  if (frames == 0) return MAVG_ERR_INVALID_ARG;  // nothing to describe, as mavg_plan
+  if (ragged_fast_path(longest, channels, grade, dtype)) {
+    LaunchPlan plan{};
+    g_plan = &plan;
+    const int c = ragged_fast_launch(kPlanIn, kPlanOut, kPlanOff, rows, frames, longest, channels, grade, dtype, nullptr);
+    g_plan = nullptr;
+    if (c != MAVG_OK) return c;
+    if (grade == 1)  // the flat copy over the packed stream
+      snprintf(buf, buflen, "ragged_scan<%s,C=%d,k=1> rows=%zu frames=%zu max_row_frames=%zu window=1 : %s",
+               dtype == MAVG_F32 ? "f32" : "i16", channels, rows, frames, longest, plan.text);
+    else
+      snprintf(buf, buflen, "%s", plan.text);
+    return MAVG_OK;
+  }
+  char row[sizeof(LaunchPlan::text)];
+  const int c = mavg_plan(longest * (size_t)channels, channels, grade, dtype, MAVG_ALGO_AUTO, 0, row, sizeof(row));
+  if (c != MAVG_OK) return c;
+  snprintf(buf, buflen, "ragged_loop rows=%zu max_row_frames=%zu x %s", rows, longest, row);
+  return MAVG_OK;
+}
+
+// One launch of the ragged scan where it applies (ragged_fast_path), else the single-signal
+// dispatch once per non-empty row on the same stream, every row planned before the first is
+// launched.  The host offsets are validated and drive the dispatch and the loop; the kernel reads
+// the device copy.
+int mavg_ragged_run(const void* d_in, void* d_out, const int64_t* h_offsets, const int64_t* d_offsets, size_t rows,
+                    int channels, int grade, int dtype, void* d_ws, size_t ws_bytes, void* stream) {
+  size_t frames = 0, longest = 0;
+  const int st = validate_ragged(h_offsets, rows, channels, grade, dtype, &frames, &longest);
+  if (st != MAVG_OK) return st;
+  if (frames == 0) return MAVG_OK;
+  if (d_in == nullptr || d_out == nullptr || d_offsets == nullptr) return MAVG_ERR_INVALID_ARG;
+  const size_t eb = elem_size(dtype);
+  if (!aligned(d_in, eb) || !aligned(d_out, eb) || !aligned(d_offsets, 8)) return MAVG_ERR_MISALIGNED;
+  if (ragged_fast_path(longest, channels, grade, dtype))
+    return ragged_fast_launch(d_in, d_out, d_offsets, rows, frames, longest, channels, grade, dtype,
+                              static_cast<hipStream_t>(stream));
+  // ragged_loop: one mavg_run per non-empty row (a misaligned row: two), all sharing the caller's
+  // workspace -- launches on one stream are serial and each zeroes its records
+  const size_t fb = (size_t)channels * eb;
+  auto row_run = [&](size_t r, bool dry) -> int {
+    const size_t f0 = (size_t)h_offsets[r], nf = (size_t)(h_offsets[r + 1] - h_offsets[r]);
+    if (nf == 0) return MAVG_OK;
+    return run_signal(static_cast<const char*>(d_in) + f0 * fb, static_cast<char*>(d_out) + f0 * fb,
+                      nf * (size_t)channels, channels, grade, dtype, MAVG_ALGO_AUTO, 0, nullptr, d_ws, ws_bytes, stream,
+                      dry);
+  };
+  // the workspace contract is mavg_ragged_workspace_bytes' (the longest row's, whatever the
+  // rows' alignment), not only what these rows' forms happen to need
+  const size_t need = plan_ws(longest * (size_t)channels, channels, grade, dtype,
+                              mavg_resolve_algo(longest * (size_t)channels, channels, grade, dtype, MAVG_ALGO_AUTO), 0);
+  if (need > 0 && (d_ws == nullptr || ws_bytes < need)) return MAVG_ERR_WORKSPACE;
+  if (need > 0 && !aligned(d_ws, 16)) return MAVG_ERR_MISALIGNED;
+  for (size_t r = 0; r < rows; ++r) {
     const int c = row_run(r, true);
     if (c != MAVG_OK) return c;
   }

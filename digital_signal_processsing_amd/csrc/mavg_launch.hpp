@@ -133,6 +133,27 @@ bool rows_scan_fits(int dtype, int C, size_t row_frames, int grade);
 // MAVG_ERR_UNSUPPORTED: the halo does not fit, or the launch would exceed grid_too_large
 int rows_scan_any(int dtype, int C, const RowsSig& rs, int grade, hipStream_t st);
 
+// The ragged rows scan (mavg_ragged.hpp, instantiated in mavg_ragged.hip): `rows` signals of
+// different lengths packed one after another, `nframes` frames in all, zero history, C = 1 or 2,
+// one launch.  d_offsets: the rows + 1 frame offsets in device memory (8-B aligned), the only
+// copy the kernel reads; max_row_frames (from the host's copy) sets the effective window.
+// unit / eio as RowsSig's.
+struct RaggedSig {
+  const void* in;
+  void* out;
+  const void* d_offsets;
+  size_t rows;
+  size_t nframes;
+  size_t max_row_frames;
+  bool unit = true;
+  int eio = 0;
+};
+// Whether the effective halo of min(grade, max_row_frames) frames fits the ragged kernel's LDS
+// (stage and row-start bitmask) in both of its forms, within the rows scan's 16-KiB halo limit.
+bool ragged_scan_fits(int dtype, int C, size_t max_row_frames, int grade);
+// MAVG_ERR_UNSUPPORTED: the halo does not fit, or the launch would exceed grid_too_large
+int ragged_scan_any(int dtype, int C, const RaggedSig& rs, int grade, hipStream_t st);
+
 // flat-tile scan: one workgroup per tile, carry rebuilt from the k-frame halo
 // DV: the int16 output division of the tile scan -- the magic multiply, which
 // measured faster than the fp64 product here (int16 stereo k=1024: 0.779 vs

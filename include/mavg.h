@@ -201,6 +201,78 @@ int mavg_rows_workspace_bytes(size_t rows, size_t row_frames, int channels, int 
 int mavg_rows_plan(size_t rows, size_t row_frames, int channels, int grade, int dtype,
                    int with_history, char* buf, size_t buflen);
 
+/* Ragged rows: `rows` independent signals of DIFFERENT lengths, packed one
+ * after another (CSR style).  Row r is frames [off[r], off[r+1]) of the packed
+ * stream; the batch holds off[rows] frames = off[rows] * channels samples.
+ * Every row is filtered exactly as mavg_run would filter it alone: zero
+ * history before its frame 0, divisor `grade` (also in the warm-up and when
+ * grade exceeds the row), the same int16 and fp32 arithmetic, and the rows
+ * API's isolation guarantee -- nothing of another row enters a row's sums, not
+ * even as a term that cancels.
+ *   h_offsets  rows + 1 frame offsets in HOST memory: h_offsets[0] == 0,
+ *              non-decreasing.  Empty rows are legal anywhere (several in a
+ *              row, the first, the last).  This copy is what the library
+ *              validates, what gives the longest row (max_row_frames) and what
+ *              drives the per-row loop.
+ *   d_offsets  the caller's DEVICE copy of the same rows + 1 values, 8-B
+ *              aligned: what the kernel reads.  The library never copies
+ *              between host and device.  Every index the kernel derives from
+ *              it is clamped to the tile and halo it belongs to and every
+ *              search is bounded by `rows`: a device copy that differs from the
+ *              host's gives wrong values, not an access outside the views.
+ *   d_in/d_out any sample-aligned views of off[rows] * channels samples.
+ *   d_ws       mavg_ragged_workspace_bytes() bytes, 16-B aligned (NULL when 0).
+ * Ownership, stream and capture rules are mavg_run's: no allocation, no
+ * synchronisation, nothing enqueued unless MAVG_OK is returned (MAVG_ERR_HIP
+ * excepted).  Arguments are validated first; then rows == 0 or off[rows] == 0:
+ * MAVG_OK, nothing enqueued.
+ *
+ * Status: MAVG_ERR_INVALID_ARG for a bad dtype, channels or grade, a NULL
+ * h_offsets with rows > 0, h_offsets[0] != 0, a decreasing pair, and a NULL
+ * d_offsets, d_in or d_out with work to do; MAVG_ERR_MISALIGNED for views off
+ * sample alignment or d_offsets off 8-B alignment; MAVG_ERR_UNSUPPORTED for
+ * 2^62 frames or more, or past the one-launch limit below.
+ *
+ * Dispatch (mavg_ragged_plan shows which):
+ *   ragged_scan  ONE launch of the ragged scan over the packed stream, no
+ *                workspace: channels 1 or 2, int16 grade <= 65535, and the
+ *                effective halo of min(grade, max_row_frames) frames at most
+ *                16 KiB (rows_scan's limit).  Tiles ignore row boundaries; the
+ *                row starts of a tile come from d_offsets (two bounded searches
+ *                and a bitmask in LDS per tile).  Views that are not both 16-B
+ *                aligned run its one-frame-per-lane form.  grade == 1 is the
+ *                flat copy.  There is no long-row rule: rows_scan's 64-MiB rule
+ *                was measured on uniform batches only.
+ *   ragged_loop  everything else (channels >= 3, windows and longest row both
+ *                past 16 KiB of halo, int16 grade > 65535): mavg_run's dispatch
+ *                (MAVG_ALGO_AUTO, block_size 0) once per non-empty row on
+ *                `stream`, from h_offsets -- correct, not fast.  All rows share
+ *                d_ws, sized for the longest row.  Every row is planned before
+ *                the first is launched: an error leaves the stream untouched.
+ *
+ * Supported maximum.  off[rows] < 2^62 frames (and the byte count in size_t).
+ * ragged_scan makes one launch of `block` threads per `tile_frames` frames
+ * (both in mavg_ragged_plan's text): off[rows] <= (2^32 - 1) / block *
+ * tile_frames frames, as rows_scan.  Tested on a 2.15e9-sample int16 batch,
+ * past 2^31 (tests/test_gpu_ragged.py).
+ */
+int mavg_ragged_run(const void* d_in, void* d_out, const int64_t* h_offsets,
+                    const int64_t* d_offsets, size_t rows, int channels, int grade,
+                    int dtype, void* d_ws, size_t ws_bytes, void* stream);
+
+/* Device workspace (bytes) mavg_ragged_run needs: 0 for ragged_scan; for
+ * ragged_loop what mavg_workspace_bytes gives for the longest row. */
+int mavg_ragged_workspace_bytes(const int64_t* h_offsets, size_t rows, int channels,
+                                int grade, int dtype, size_t* out_bytes);
+
+/* Describe, without launching anything, what mavg_ragged_run would do on
+ * 16-B-aligned views: "ragged_scan<...> rows=R frames=N max_row_frames=M
+ * window=min(grade,M) ... tile_frames=T ..." or "ragged_loop rows=R
+ * max_row_frames=M x <mavg_plan's text for the longest row>" (up to ~300
+ * characters).  An empty batch has no plan: MAVG_ERR_INVALID_ARG. */
+int mavg_ragged_plan(const int64_t* h_offsets, size_t rows, int channels, int grade,
+                     int dtype, char* buf, size_t buflen);
+
 /* Describe, without launching anything, the kernel and launch geometry
  * mavg_run would use for these arguments on 16-B-aligned views
  * (e.g. "tile_scan<f32,...> grid=... block=256 ..."). */
