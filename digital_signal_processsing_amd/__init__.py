@@ -83,6 +83,81 @@ def _stream_handle(stream, device) -> int:
     return stream.cuda_stream
 
 
+def _check_device_pair(x, out) -> None:
+    if not (x.is_cuda and out.is_cuda):
+        raise ValueError("x and out must be device tensors (libmavg has no CPU path)")
+    if not (x.is_contiguous() and out.is_contiguous()):
+        raise ValueError("x and out must be contiguous")
+
+
+def _check_device_x(x) -> None:
+    if not x.is_cuda:
+        raise ValueError("x must be a device tensor (libmavg has no CPU path)")
+    if not x.is_contiguous():
+        raise ValueError("x must be contiguous")
+
+
+def _history_ptr(history, x, samples: int, what: str):
+    """The history's device pointer (None without one); it must hold ``samples`` = ``what`` samples."""
+    if history is None:
+        return None
+    if history.dtype != x.dtype or not history.is_cuda or not history.is_contiguous():
+        raise ValueError("history must be a contiguous device tensor of x's dtype")
+    if history.numel() != samples:
+        raise ValueError(f"history must hold {what} = {samples} samples")
+    return history.data_ptr() if history.numel() else None
+
+
+def _on_stream(stream, make):
+    """``make()`` with the launch stream current: a block the caching allocator hands out there is
+    free with respect to that stream's pending work (one taken on another stream could still be
+    in use by kernels queued there, and record_stream only protects the free)."""
+    torch = _torch()
+    with torch.cuda.stream(stream) if stream is not None else _nullctx():
+        return make()
+
+
+def _check_workspace_tensor(workspace) -> int:
+    """A caller's workspace tensor; its size in bytes."""
+    if not (workspace.is_cuda and workspace.is_contiguous()):
+        raise ValueError("workspace must be a contiguous device tensor")
+    return workspace.numel() * workspace.element_size()
+
+
+def _loop_workspace(ws_n: int, workspace, stream, device, query: str):
+    """(workspace tensor or None, its bytes) for the per-row loops of the batch calls; ``query``
+    names the function that tells the size."""
+    torch = _torch()
+    if not ws_n:
+        return None, 0
+    if workspace is not None:
+        # (a workspace that is too small goes to the library: MAVG_ERR_WORKSPACE, nothing enqueued)
+        return workspace, _check_workspace_tensor(workspace)
+    if torch.cuda.is_current_stream_capturing():
+        raise ValueError(f"this batch runs the per-row loop, which needs a {ws_n}-byte workspace: "
+                         f"inside a graph capture pass workspace= (see {query}())")
+    return _on_stream(stream, lambda: torch.empty(ws_n, dtype=torch.uint8, device=device)), ws_n
+
+
+def _with_out(x, stream, into, inputs):
+    """``out = empty_like(x)`` filled by ``into(out)``.  On a launch stream other than the
+    current one, the launch stream waits for the current one (where ``inputs`` come from),
+    ``out`` is allocated on the launch stream, and the caching allocator is kept from handing
+    the inputs' blocks out again before the kernel that reads them there ends."""
+    torch = _torch()
+    if stream is None or stream == torch.cuda.current_stream(x.device):
+        out = torch.empty_like(x)
+        into(out)
+        return out
+    stream.wait_stream(torch.cuda.current_stream(x.device))
+    out = _on_stream(stream, lambda: torch.empty_like(x))
+    into(out)
+    for t in inputs:
+        if t is not None:
+            t.record_stream(stream)
+    return out
+
+
 def workspace_bytes(n: int, grade: int, channels: int = 1, dtype: int = F32, algo="auto",
                     block_size: int = 0, library: Optional[str] = None) -> int:
     import ctypes
@@ -119,43 +194,27 @@ def moving_average_into(x, out, grade: int, channels: int = 1, algo="auto", hist
     ``library``: path of another build of the same ABI (the debug build,
     ``_lib.DEBUG_LIB_PATH``); default the release ``libmavg.so``."""
     torch = _torch()
-    if not (x.is_cuda and out.is_cuda):
-        raise ValueError("x and out must be device tensors (libmavg has no CPU path)")
-    if not (x.is_contiguous() and out.is_contiguous()):
-        raise ValueError("x and out must be contiguous")
+    _check_device_pair(x, out)
     if x.dtype != out.dtype or x.numel() != out.numel():
         raise ValueError("x and out must have the same dtype and size")
     dt = _dtype_code(x)
-    hist_ptr = None
-    if history is not None:
-        if history.dtype != x.dtype or not history.is_cuda or not history.is_contiguous():
-            raise ValueError("history must be a contiguous device tensor of x's dtype")
-        if history.numel() != (grade - 1) * channels:
-            raise ValueError(f"history must hold (grade-1)*channels = {(grade - 1) * channels} samples")
-        hist_ptr = history.data_ptr() if history.numel() else None
+    hist_ptr = _history_ptr(history, x, (grade - 1) * channels, "(grade-1)*channels")
     # workspace (look-back scan only): from torch's caching allocator, tied to
     # the launch stream so it is not handed out again before the kernel ends
     ws_n = workspace_bytes(x.numel(), grade, channels, dt, algo, block_size, library)
     ws = None
     if ws_n and workspace is not None:
-        if not (workspace.is_cuda and workspace.is_contiguous()):
-            raise ValueError("workspace must be a contiguous device tensor")
-        if workspace.numel() * workspace.element_size() < ws_n:
-            raise ValueError(f"workspace holds {workspace.numel() * workspace.element_size()} bytes, "
-                             f"the launch needs {ws_n}")
-        ws, ws_n = workspace, workspace.numel() * workspace.element_size()
+        have = _check_workspace_tensor(workspace)
+        if have < ws_n:
+            raise ValueError(f"workspace holds {have} bytes, the launch needs {ws_n}")
+        ws, ws_n = workspace, have
     elif ws_n:
         if torch.cuda.is_current_stream_capturing():
             # a workspace taken from the capture's private pool is freed again
             # before the capture ends; pass one that outlives the graph
             raise ValueError(f"grade={grade} uses the look-back scan, which needs a {ws_n}-byte workspace: "
                              "inside a graph capture pass workspace= (see workspace_bytes())")
-        # allocated on the launch stream itself: a block the caching allocator
-        # hands out there is free with respect to that stream's pending work
-        # (one taken on another stream could still be in use by kernels queued
-        # there, and record_stream only protects the free)
-        with torch.cuda.stream(stream) if stream is not None else _nullctx():
-            ws = torch.empty(ws_n, dtype=torch.uint8, device=x.device)
+        ws = _on_stream(stream, lambda: torch.empty(ws_n, dtype=torch.uint8, device=x.device))
     st = _lib.load(library).mavg_run(x.data_ptr(), out.data_ptr(), x.numel(), channels, grade, dt,
                               _algo_code(algo), block_size, hist_ptr,
                               ws.data_ptr() if ws is not None else None, ws_n,
@@ -166,23 +225,8 @@ def moving_average_into(x, out, grade: int, channels: int = 1, algo="auto", hist
 def moving_average(x, grade: int, channels: int = 1, algo="auto", history=None,
                    block_size: int = 0, stream=None, library: Optional[str] = None):
     """Causal ``grade``-frame moving average of an interleaved signal ``x``."""
-    torch = _torch()
-    if stream is not None and stream != torch.cuda.current_stream(x.device):
-        # x (and history) come from the caller's current stream: the launch
-        # stream waits for it, and `out` is allocated on the launch stream
-        stream.wait_stream(torch.cuda.current_stream(x.device))
-        with torch.cuda.stream(stream):
-            out = torch.empty_like(x)
-        moving_average_into(x, out, grade, channels, algo, history, block_size, stream, library=library)
-        # the kernel reads x and history on `stream`: keep the caching
-        # allocator from handing their blocks out again before it ends
-        x.record_stream(stream)
-        if history is not None:
-            history.record_stream(stream)
-        return out
-    out = torch.empty_like(x)
-    moving_average_into(x, out, grade, channels, algo, history, block_size, stream, library=library)
-    return out
+    return _with_out(x, stream, lambda out: moving_average_into(x, out, grade, channels, algo, history, block_size,
+                                                                stream, library=library), (x, history))
 
 
 def rows_workspace_bytes(rows: int, row_frames: int, grade: int, channels: int = 1, dtype: int = F32,
@@ -235,36 +279,14 @@ def moving_average_rows_into(x, out, grade: int, channels: int = 1, history=None
     ``history``: optional, ``rows * (grade-1) * channels`` samples, row r's history at
     ``r * (grade-1) * channels``.  ``workspace``: as in ``moving_average_into``; only the per-row
     loop needs one (``rows_workspace_bytes``), the one-launch rows scan needs none."""
-    torch = _torch()
-    if not (x.is_cuda and out.is_cuda):
-        raise ValueError("x and out must be device tensors (libmavg has no CPU path)")
-    if not (x.is_contiguous() and out.is_contiguous()):
-        raise ValueError("x and out must be contiguous")
+    _check_device_pair(x, out)
     if x.dtype != out.dtype or x.shape != out.shape:
         raise ValueError("x and out must have the same dtype and shape")
     dt = _dtype_code(x)
     rows, row_frames = _rows_shape(x, channels)
-    hist_ptr = None
-    if history is not None:
-        if history.dtype != x.dtype or not history.is_cuda or not history.is_contiguous():
-            raise ValueError("history must be a contiguous device tensor of x's dtype")
-        if history.numel() != rows * (grade - 1) * channels:
-            raise ValueError(f"history must hold rows*(grade-1)*channels = {rows * (grade - 1) * channels} samples")
-        hist_ptr = history.data_ptr() if history.numel() else None
+    hist_ptr = _history_ptr(history, x, rows * (grade - 1) * channels, "rows*(grade-1)*channels")
     ws_n = rows_workspace_bytes(rows, row_frames, grade, channels, dt, hist_ptr is not None, library)
-    ws = None
-    if ws_n and workspace is not None:
-        if not (workspace.is_cuda and workspace.is_contiguous()):
-            raise ValueError("workspace must be a contiguous device tensor")
-        # (a workspace that is too small goes to the library: MAVG_ERR_WORKSPACE, nothing enqueued)
-        ws, ws_n = workspace, workspace.numel() * workspace.element_size()
-    elif ws_n:
-        if torch.cuda.is_current_stream_capturing():
-            raise ValueError(f"this batch runs the per-row loop, which needs a {ws_n}-byte workspace: "
-                             "inside a graph capture pass workspace= (see rows_workspace_bytes())")
-        # on the launch stream itself, as in moving_average_into
-        with torch.cuda.stream(stream) if stream is not None else _nullctx():
-            ws = torch.empty(ws_n, dtype=torch.uint8, device=x.device)
+    ws, ws_n = _loop_workspace(ws_n, workspace, stream, x.device, "rows_workspace_bytes")
     st = _lib.load(library).mavg_rows_run(x.data_ptr(), out.data_ptr(), rows, row_frames, channels, grade, dt,
                                           hist_ptr, ws.data_ptr() if ws is not None else None, ws_n,
                                           _stream_handle(stream, x.device))
@@ -279,25 +301,10 @@ def moving_average_rows(x, grade: int, channels: int = 1, history=None, stream=N
     ``channels == 1``: the last dimension is time, all leading dimensions are rows -- planar audio
     ``[C, T]``, batches ``[B, T]``, ``[B, C, T]``.  ``channels == C > 1``: ``[..., T, C]``,
     interleaved frames.  The output has ``x``'s shape."""
-    torch = _torch()
     _rows_shape(x, channels)
-    if not x.is_cuda:
-        raise ValueError("x must be a device tensor (libmavg has no CPU path)")
-    if not x.is_contiguous():
-        raise ValueError("x must be contiguous")
-    if stream is not None and stream != torch.cuda.current_stream(x.device):
-        # as moving_average: the launch stream waits for x's, `out` is allocated on it
-        stream.wait_stream(torch.cuda.current_stream(x.device))
-        with torch.cuda.stream(stream):
-            out = torch.empty_like(x)
-        moving_average_rows_into(x, out, grade, channels, history, stream, library=library)
-        x.record_stream(stream)
-        if history is not None:
-            history.record_stream(stream)
-        return out
-    out = torch.empty_like(x)
-    moving_average_rows_into(x, out, grade, channels, history, stream, library=library)
-    return out
+    _check_device_x(x)
+    return _with_out(x, stream, lambda out: moving_average_rows_into(x, out, grade, channels, history, stream,
+                                                                     library=library), (x, history))
 
 
 def _host_offsets(offsets, lengths):
@@ -391,10 +398,7 @@ def moving_average_ragged_into(x, out, grade: int, offsets=None, lengths=None, c
     capture cannot do -- pass it there.  ``workspace``: as in ``moving_average_rows_into``; only
     the per-row loop needs one (``ragged_workspace_bytes``)."""
     torch = _torch()
-    if not (x.is_cuda and out.is_cuda):
-        raise ValueError("x and out must be device tensors (libmavg has no CPU path)")
-    if not (x.is_contiguous() and out.is_contiguous()):
-        raise ValueError("x and out must be contiguous")
+    _check_device_pair(x, out)
     if x.dtype != out.dtype or x.shape != out.shape:
         raise ValueError("x and out must have the same dtype and shape")
     dt = _dtype_code(x)
@@ -416,20 +420,8 @@ def moving_average_ragged_into(x, out, grade: int, offsets=None, lengths=None, c
             raise ValueError("the offsets would be uploaded to the device here: inside a graph capture pass "
                              "offsets_device= (an int64 device tensor of the rows + 1 offsets)")
         # on the launch stream itself (a copy from pageable host memory returns when it is staged)
-        with torch.cuda.stream(stream) if stream is not None else _nullctx():
-            offsets_device = off.to(x.device)
-    ws = None
-    if ws_n and workspace is not None:
-        if not (workspace.is_cuda and workspace.is_contiguous()):
-            raise ValueError("workspace must be a contiguous device tensor")
-        # (a workspace that is too small goes to the library: MAVG_ERR_WORKSPACE, nothing enqueued)
-        ws, ws_n = workspace, workspace.numel() * workspace.element_size()
-    elif ws_n:
-        if torch.cuda.is_current_stream_capturing():
-            raise ValueError(f"this batch runs the per-row loop, which needs a {ws_n}-byte workspace: "
-                             "inside a graph capture pass workspace= (see ragged_workspace_bytes())")
-        with torch.cuda.stream(stream) if stream is not None else _nullctx():
-            ws = torch.empty(ws_n, dtype=torch.uint8, device=x.device)
+        offsets_device = _on_stream(stream, lambda: off.to(x.device))
+    ws, ws_n = _loop_workspace(ws_n, workspace, stream, x.device, "ragged_workspace_bytes")
     st = _lib.load(library).mavg_ragged_run(x.data_ptr(), out.data_ptr(), _offsets_ptr(off),
                                             offsets_device.data_ptr(), rows, channels, grade, dt,
                                             ws.data_ptr() if ws is not None else None, ws_n,
@@ -445,23 +437,10 @@ def moving_average_ragged(x, grade: int, offsets=None, lengths=None, channels: i
     filtered as ``moving_average`` would filter it alone (zero history before its first frame,
     divisor ``grade``), in one launch where the ragged scan applies (``ragged_plan``).  Arguments
     as ``moving_average_ragged_into``; the output has ``x``'s shape."""
-    torch = _torch()
     _ragged_frames(x, channels)
-    if not x.is_cuda:
-        raise ValueError("x must be a device tensor (libmavg has no CPU path)")
-    if not x.is_contiguous():
-        raise ValueError("x must be contiguous")
-    if stream is not None and stream != torch.cuda.current_stream(x.device):
-        # as moving_average: the launch stream waits for x's, `out` is allocated on it
-        stream.wait_stream(torch.cuda.current_stream(x.device))
-        with torch.cuda.stream(stream):
-            out = torch.empty_like(x)
-        moving_average_ragged_into(x, out, grade, offsets, lengths, channels, offsets_device, stream, library=library)
-        x.record_stream(stream)
-        return out
-    out = torch.empty_like(x)
-    moving_average_ragged_into(x, out, grade, offsets, lengths, channels, offsets_device, stream, library=library)
-    return out
+    _check_device_x(x)
+    return _with_out(x, stream, lambda out: moving_average_ragged_into(x, out, grade, offsets, lengths, channels,
+                                                                       offsets_device, stream, library=library), (x,))
 
 
 def fill_synthetic(n: int, dtype=None, seed: int = 0x5EED, offset: int = 0, dist: int = 0,

@@ -133,6 +133,27 @@ int launch_algo(int algo, int dtype, int C, const Sig& sg, int k, int block, hip
   }
 }
 
+// 16-B-aligned dummy device pointers for plan mode: nothing is launched or dereferenced
+const void* const kPlanIn = reinterpret_cast<const void*>(uintptr_t(1) << 20);
+void* const kPlanOut = reinterpret_cast<void*>(uintptr_t(1) << 21);
+const void* const kPlanOff = reinterpret_cast<const void*>(uintptr_t(1) << 22);
+
+// Plan mode for one scope: the launchers describe the launch into `plan` instead of making it.
+struct PlanScope {
+  LaunchPlan plan{};
+  PlanScope() { g_plan = &plan; }
+  ~PlanScope() { g_plan = nullptr; }
+  PlanScope(const PlanScope&) = delete;
+  PlanScope& operator=(const PlanScope&) = delete;
+};
+
+// The caller's workspace against the `need` bytes of a plan: present, large enough, 16-B aligned.
+int check_workspace(size_t need, const void* d_ws, size_t ws_bytes) {
+  if (need > 0 && (d_ws == nullptr || ws_bytes < need)) return MAVG_ERR_WORKSPACE;
+  if (need > 0 && !aligned(d_ws, 16)) return MAVG_ERR_MISALIGNED;
+  return MAVG_OK;
+}
+
 // Workspace the launch(es) for this problem need, whatever the pointers'
 // alignment: a vector algorithm on a misaligned view may run its frame-unit
 // form over the whole signal instead (more, smaller look-ahead tiles).
@@ -140,13 +161,10 @@ size_t plan_ws(size_t n, int C, int k, int dtype, int algo, int block) {
   size_t need = 0;
   const int forms[2] = {algo, scalar_form(algo)};
   for (int i = 0; i < (forms[1] == forms[0] ? 1 : 2); ++i) {
-    LaunchPlan plan{};
-    g_plan = &plan;
-    const Sig sg{reinterpret_cast<const void*>(uintptr_t(1) << 20), reinterpret_cast<void*>(uintptr_t(1) << 21),
-                 nullptr, (long long)(n / (size_t)C)};
-    const int st = launch_algo(forms[i], dtype, C, sg, k, block, nullptr, Workspace{});
-    g_plan = nullptr;
-    if (st == MAVG_OK) need = std::max(need, plan.ws_bytes);
+    PlanScope ps;
+    const Sig sg{kPlanIn, kPlanOut, nullptr, (long long)(n / (size_t)C)};
+    if (launch_algo(forms[i], dtype, C, sg, k, block, nullptr, Workspace{}) == MAVG_OK)
+      need = std::max(need, ps.plan.ws_bytes);
   }
   return need;
 }
@@ -188,14 +206,9 @@ int run_signal(const void* d_in, void* d_out, size_t n_samples, int channels, in
   };
   // one launch in plan mode: its status and its workspace against the caller's
   auto check = [&](int a, const Sig& sg) -> int {
-    LaunchPlan plan{};
-    g_plan = &plan;
+    PlanScope ps;
     const int c = launch_algo(a, dtype, C, sg, grade, block_size, nullptr, ws);
-    g_plan = nullptr;
-    if (c != MAVG_OK) return c;
-    if (plan.ws_bytes > 0 && (d_ws == nullptr || ws_bytes < plan.ws_bytes)) return MAVG_ERR_WORKSPACE;
-    if (plan.ws_bytes > 0 && !aligned(d_ws, 16)) return MAVG_ERR_MISALIGNED;
-    return MAVG_OK;
+    return c != MAVG_OK ? c : check_workspace(ps.plan.ws_bytes, d_ws, ws_bytes);
   };
   auto single = [&](int a, const Sig& sg) -> int {
     return dry ? check(a, sg) : launch_algo(a, dtype, C, sg, grade, block_size, s, ws);
@@ -224,6 +237,29 @@ int run_signal(const void* d_in, void* d_out, size_t n_samples, int channels, in
   st = launch_algo(sf, dtype, C, head, grade, block_size, s, ws);
   if (st != MAVG_OK || p == nframes) return st;
   return launch_algo(algo, dtype, C, body, grade, block_size, s, ws);
+}
+
+// The per-row loops of mavg_rows_run and mavg_ragged_run.  The workspace contract is the
+// *_workspace_bytes call's -- what a signal of `ws_samples` samples needs, whatever the rows'
+// alignment, not only what these rows' forms happen to need.  Then the first `ndry` rows are
+// dry-run and every row is launched: row_run(r, dry).
+template <typename RowRun>
+int run_row_loop(size_t rows, size_t ndry, size_t ws_samples, int C, int k, int dtype, const void* d_ws,
+                 size_t ws_bytes, RowRun row_run) {
+  const size_t need = plan_ws(ws_samples, C, k, dtype, mavg_resolve_algo(ws_samples, C, k, dtype, MAVG_ALGO_AUTO), 0);
+  int c = check_workspace(need, d_ws, ws_bytes);
+  for (size_t r = 0; c == MAVG_OK && r < ndry; ++r) c = row_run(r, true);
+  for (size_t r = 0; c == MAVG_OK && r < rows; ++r) c = row_run(r, false);
+  return c;
+}
+
+// unit / eio of a batch launch (RowsSig, RaggedSig) from its views' alignment
+template <typename S>
+S with_alignment(S rs, int C, int dtype) {
+  const size_t fb = elem_size(dtype) * (size_t)C;
+  rs.unit = aligned(rs.in, 16) && aligned(rs.out, 16);
+  rs.eio = !rs.unit && (!aligned(rs.in, fb) || !aligned(rs.out, fb)) ? 1 : 0;
+  return rs;
 }
 
 // ---- rows (mavg_rows_run) -------------------------------------------------------------------
@@ -265,11 +301,7 @@ bool rows_fast_path(size_t row_frames, int C, int k, int dtype, bool with_histor
 int rows_fast_launch(const void* in, void* out, size_t rows, size_t row_frames, size_t frames, int C, int k, int dtype,
                      hipStream_t s) {
   if (k == 1) return launch_identity(dtype, C, Sig{in, out, nullptr, (long long)frames}, s);
-  RowsSig rs{in, out, rows, row_frames};
-  const size_t fb = elem_size(dtype) * (size_t)C;
-  rs.unit = aligned(in, 16) && aligned(out, 16);
-  rs.eio = !rs.unit && (!aligned(in, fb) || !aligned(out, fb)) ? 1 : 0;
-  return rows_scan_any(dtype, C, rs, k, s);
+  return rows_scan_any(dtype, C, with_alignment(RowsSig{in, out, rows, row_frames}, C, dtype), k, s);
 }
 
 // Rows whose alignment classes cover the batch's: row r's views sit r * row_bytes further, and
@@ -316,17 +348,8 @@ bool ragged_fast_path(size_t longest, int C, int k, int dtype) {
 int ragged_fast_launch(const void* in, void* out, const void* d_off, size_t rows, size_t frames, size_t longest, int C,
                        int k, int dtype, hipStream_t s) {
   if (k == 1) return launch_identity(dtype, C, Sig{in, out, nullptr, (long long)frames}, s);
-  RaggedSig rs{in, out, d_off, rows, frames, longest};
-  const size_t fb = elem_size(dtype) * (size_t)C;
-  rs.unit = aligned(in, 16) && aligned(out, 16);
-  rs.eio = !rs.unit && (!aligned(in, fb) || !aligned(out, fb)) ? 1 : 0;
-  return ragged_scan_any(dtype, C, rs, k, s);
+  return ragged_scan_any(dtype, C, with_alignment(RaggedSig{in, out, d_off, rows, frames, longest}, C, dtype), k, s);
 }
-
-// 16-B-aligned dummy device pointers for plan mode: nothing is launched or dereferenced
-const void* const kPlanIn = reinterpret_cast<const void*>(uintptr_t(1) << 20);
-void* const kPlanOut = reinterpret_cast<void*>(uintptr_t(1) << 21);
-const void* const kPlanOff = reinterpret_cast<const void*>(uintptr_t(1) << 22);
 
 }  // namespace
 
@@ -403,16 +426,12 @@ int mavg_plan(size_t n_samples, int channels, int grade, int dtype, int algo, in
   if (n_samples == 0) return MAVG_ERR_INVALID_ARG;
   const int st0 = validate(n_samples, channels, grade, dtype, algo, block_size);
   if (st0 != MAVG_OK) return st0;
-  LaunchPlan plan{};
-  g_plan = &plan;
-  // 16-B-aligned dummy device pointers: nothing is launched or dereferenced in plan mode
-  const Sig sg{reinterpret_cast<const void*>(uintptr_t(1) << 20), reinterpret_cast<void*>(uintptr_t(1) << 21),
-               nullptr, (long long)(n_samples / (size_t)channels)};
+  PlanScope ps;
+  const Sig sg{kPlanIn, kPlanOut, nullptr, (long long)(n_samples / (size_t)channels)};
   const int st = launch_algo(mavg_resolve_algo(n_samples, channels, grade, dtype, algo), dtype, channels, sg, grade,
                              block_size, nullptr, Workspace{});
-  g_plan = nullptr;
   if (st != MAVG_OK) return st;
-  snprintf(buf, buflen, "%s", plan.text);
+  snprintf(buf, buflen, "%s", ps.plan.text);
   return MAVG_OK;
 }
 
@@ -453,13 +472,8 @@ int mavg_rows_workspace_bytes(size_t rows, size_t row_frames, int channels, int 
   if (frames == 0) return MAVG_OK;
   if (rows_fast_path(row_frames, channels, grade, dtype, with_history != 0)) {
     // no workspace; the launch's own limit (grid_too_large) shows here as it does in mavg_rows_run
-    LaunchPlan plan{};
-    g_plan = &plan;
-    const int c = rows_fast_launch(reinterpret_cast<const void*>(uintptr_t(1) << 20),
-                                   reinterpret_cast<void*>(uintptr_t(1) << 21), rows, row_frames, frames, channels,
-                                   grade, dtype, nullptr);
-    g_plan = nullptr;
-    return c;
+    PlanScope ps;
+    return rows_fast_launch(kPlanIn, kPlanOut, rows, row_frames, frames, channels, grade, dtype, nullptr);
   }
   return mavg_workspace_bytes(row_frames * (size_t)channels, channels, grade, dtype, MAVG_ALGO_AUTO, 0, out_bytes);
 }
@@ -473,19 +487,14 @@ int mavg_rows_plan(size_t rows, size_t row_frames, int channels, int grade, int 
   const int st = validate_rows(rows, row_frames, channels, grade, dtype, &frames);
   if (st != MAVG_OK) return st;
   if (rows_fast_path(row_frames, channels, grade, dtype, with_history != 0)) {
-    LaunchPlan plan{};
-    g_plan = &plan;
-    // 16-B-aligned dummy device pointers: nothing is launched or dereferenced in plan mode
-    const int c = rows_fast_launch(reinterpret_cast<const void*>(uintptr_t(1) << 20),
-                                   reinterpret_cast<void*>(uintptr_t(1) << 21), rows, row_frames, frames, channels,
-                                   grade, dtype, nullptr);
-    g_plan = nullptr;
+    PlanScope ps;
+    const int c = rows_fast_launch(kPlanIn, kPlanOut, rows, row_frames, frames, channels, grade, dtype, nullptr);
     if (c != MAVG_OK) return c;
     if (grade == 1)  // the flat copy over the whole batch
       snprintf(buf, buflen, "rows_scan<%s,C=%d,k=1> rows=%zu row_frames=%zu: %s", dtype == MAVG_F32 ? "f32" : "i16",
-               channels, rows, row_frames, plan.text);
+               channels, rows, row_frames, ps.plan.text);
     else
-      snprintf(buf, buflen, "%s", plan.text);
+      snprintf(buf, buflen, "%s", ps.plan.text);
     return MAVG_OK;
   }
   char row[sizeof(LaunchPlan::text)];
@@ -520,21 +529,7 @@ int mavg_rows_run(const void* d_in, void* d_out, size_t rows, size_t row_frames,
     return run_signal(static_cast<const char*>(d_in) + r * row_bytes, static_cast<char*>(d_out) + r * row_bytes,
                       row_samples, channels, grade, dtype, MAVG_ALGO_AUTO, 0, h, d_ws, ws_bytes, stream, dry);
   };
-  // the workspace contract is mavg_rows_workspace_bytes' (whatever the rows' alignment), not
-  // only what these rows' forms happen to need
-  const size_t need = plan_ws(row_samples, channels, grade, dtype,
-                              mavg_resolve_algo(row_samples, channels, grade, dtype, MAVG_ALGO_AUTO), 0);
-  if (need > 0 && (d_ws == nullptr || ws_bytes < need)) return MAVG_ERR_WORKSPACE;
-  if (need > 0 && !aligned(d_ws, 16)) return MAVG_ERR_MISALIGNED;
-  for (size_t r = 0; r < rows_alignment_period(rows); ++r) {
-    const int c = row_run(r, true);
-    if (c != MAVG_OK) return c;
-  }
-  for (size_t r = 0; r < rows; ++r) {
-    const int c = row_run(r, false);
-    if (c != MAVG_OK) return c;
-  }
-  return MAVG_OK;
+  return run_row_loop(rows, rows_alignment_period(rows), row_samples, channels, grade, dtype, d_ws, ws_bytes, row_run);
 }
 
 int mavg_ragged_workspace_bytes(const int64_t* h_offsets, size_t rows, int channels, int grade, int dtype,
@@ -547,11 +542,8 @@ int mavg_ragged_workspace_bytes(const int64_t* h_offsets, size_t rows, int chann
   if (frames == 0) return MAVG_OK;
   if (ragged_fast_path(longest, channels, grade, dtype)) {
     // no workspace; the launch's own limit (grid_too_large) shows here as it does in mavg_ragged_run
-    LaunchPlan plan{};
-    g_plan = &plan;
-    const int c = ragged_fast_launch(kPlanIn, kPlanOut, kPlanOff, rows, frames, longest, channels, grade, dtype, nullptr);
-    g_plan = nullptr;
-    return c;
+    PlanScope ps;
+    return ragged_fast_launch(kPlanIn, kPlanOut, kPlanOff, rows, frames, longest, channels, grade, dtype, nullptr);
   }
   return mavg_workspace_bytes(longest * (size_t)channels, channels, grade, dtype, MAVG_ALGO_AUTO, 0, out_bytes);
 }
@@ -565,16 +557,14 @@ int mavg_ragged_plan(const int64_t* h_offsets, size_t rows, int channels, int gr
   if (st != MAVG_OK) return st;
   if (frames == 0) return MAVG_ERR_INVALID_ARG;  // nothing to describe, as mavg_plan
   if (ragged_fast_path(longest, channels, grade, dtype)) {
-    LaunchPlan plan{};
-    g_plan = &plan;
+    PlanScope ps;
     const int c = ragged_fast_launch(kPlanIn, kPlanOut, kPlanOff, rows, frames, longest, channels, grade, dtype, nullptr);
-    g_plan = nullptr;
     if (c != MAVG_OK) return c;
     if (grade == 1)  // the flat copy over the packed stream
       snprintf(buf, buflen, "ragged_scan<%s,C=%d,k=1> rows=%zu frames=%zu max_row_frames=%zu window=1 : %s",
-               dtype == MAVG_F32 ? "f32" : "i16", channels, rows, frames, longest, plan.text);
+               dtype == MAVG_F32 ? "f32" : "i16", channels, rows, frames, longest, ps.plan.text);
     else
-      snprintf(buf, buflen, "%s", plan.text);
+      snprintf(buf, buflen, "%s", ps.plan.text);
     return MAVG_OK;
   }
   char row[sizeof(LaunchPlan::text)];
@@ -610,21 +600,8 @@ int mavg_ragged_run(const void* d_in, void* d_out, const int64_t* h_offsets, con
                       nf * (size_t)channels, channels, grade, dtype, MAVG_ALGO_AUTO, 0, nullptr, d_ws, ws_bytes, stream,
                       dry);
   };
-  // the workspace contract is mavg_ragged_workspace_bytes' (the longest row's, whatever the
-  // rows' alignment), not only what these rows' forms happen to need
-  const size_t need = plan_ws(longest * (size_t)channels, channels, grade, dtype,
-                              mavg_resolve_algo(longest * (size_t)channels, channels, grade, dtype, MAVG_ALGO_AUTO), 0);
-  if (need > 0 && (d_ws == nullptr || ws_bytes < need)) return MAVG_ERR_WORKSPACE;
-  if (need > 0 && !aligned(d_ws, 16)) return MAVG_ERR_MISALIGNED;
-  for (size_t r = 0; r < rows; ++r) {
-    const int c = row_run(r, true);
-    if (c != MAVG_OK) return c;
-  }
-  for (size_t r = 0; r < rows; ++r) {
-    const int c = row_run(r, false);
-    if (c != MAVG_OK) return c;
-  }
-  return MAVG_OK;
+  // (the workspace: the longest row's; every row is dry-run -- their lengths and alignments differ)
+  return run_row_loop(rows, rows, longest * (size_t)channels, channels, grade, dtype, d_ws, ws_bytes, row_run);
 }
 
 }  // extern "C"

@@ -120,7 +120,7 @@ __device__ __forceinline__ void wave_incl_scan_n(A (&v)[N]) {
   for (int i = 0; i < N; ++i) v[i] += dpp<0x143, 0xc, 0xf>(v[i]);
 }
 
-// Segmented inclusive scan across the 64 lanes (mavg_rows.hpp): N values per lane that share one
+// Segmented inclusive scan across the 64 lanes (mavg_segscan.hpp): N values per lane that share one
 // flag, "a segment starts in this lane".  The operator on (flag, value) pairs is
 //     (fa, a) (+) (fb, b) = (fa | fb, fb ? b : a + b)
 // -- associative, so the six steps of wave_incl_scan apply unchanged: at each step a lane adds the

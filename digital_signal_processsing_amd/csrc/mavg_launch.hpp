@@ -114,7 +114,7 @@ int scan_i16_wide(int C, bool vec, bool hs, const Sig& sg, int k, int block, hip
 int direct_any(int dtype, bool wide, int C, int width, const Sig& sg, int k, int block, hipStream_t st);
 int naive_any(int dtype, bool wide, const Sig& sg, int C, int k, int block, hipStream_t st);
 
-// The batched rows scan (mavg_rows.hpp, instantiated in mavg_rows.hip): `rows` signals of
+// The batched rows scan (mavg_segscan.hpp DenseRows, instantiated in mavg_segscan.hip): `rows` signals of
 // `row_frames` frames each, dense, zero history, C = 1 or 2, one launch.
 //   unit  the 16-B-unit form (both views 16-B aligned); else the frame-unit (F = 1) form
 //   eio   frame-unit form on views that are only element-aligned (UnitIO::gload)
@@ -133,7 +133,7 @@ bool rows_scan_fits(int dtype, int C, size_t row_frames, int grade);
 // MAVG_ERR_UNSUPPORTED: the halo does not fit, or the launch would exceed grid_too_large
 int rows_scan_any(int dtype, int C, const RowsSig& rs, int grade, hipStream_t st);
 
-// The ragged rows scan (mavg_ragged.hpp, instantiated in mavg_ragged.hip): `rows` signals of
+// The ragged rows scan (mavg_segscan.hpp RaggedRows, instantiated in mavg_segscan.hip): `rows` signals of
 // different lengths packed one after another, `nframes` frames in all, zero history, C = 1 or 2,
 // one launch.  d_offsets: the rows + 1 frame offsets in device memory (8-B aligned), the only
 // copy the kernel reads; max_row_frames (from the host's copy) sets the effective window.

@@ -1,5 +1,5 @@
 """GPU tests of the ragged rows API (moving_average_ragged -> mavg_ragged_run): the one-launch
-ragged scan (mavg_ragged.hpp) and the per-row loop fallback.
+ragged scan (mavg_segscan.hpp) and the per-row loop fallback.
 
 The reference everywhere is the CPU oracle applied PER ROW (oracle.mavg_i16 / mavg_f32 of each
 row's slice of the packed stream).  Pass criteria, those of tests/test_gpu_rows.py: int16

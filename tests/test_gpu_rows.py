@@ -1,5 +1,5 @@
 """GPU tests of the batched rows API (moving_average_rows -> mavg_rows_run): the one-launch
-segmented rows scan (mavg_rows.hpp) and the per-row loop fallback.
+segmented rows scan (mavg_segscan.hpp) and the per-row loop fallback.
 
 The reference everywhere is the CPU oracle applied PER ROW (oracle.mavg_i16 / mavg_f32 of
 x[r]).  Pass criteria: int16 bit-exact; fp32 on int16-valued data (dist 0) bit-equal (the fp64
