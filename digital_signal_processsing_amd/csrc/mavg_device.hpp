@@ -30,6 +30,22 @@ namespace mavg {
 constexpr int kWG = 256;          // threads per workgroup (4 wave64s)
 constexpr int kNW = kWG / 64;     // waves per workgroup
 
+// The dynamic-LDS budgets of a workgroup.  The launchers refuse a layout (the kernels' *Lds
+// structs) past its budget and the debug build checks the same bound in the kernel.
+constexpr size_t kLdsBudget = 64 * 1024;  // keeps >= 2 workgroups per CU
+// A 1024-thread workgroup may take 80 KiB: two of them still fill a CU's 32
+// wave slots within its 160 KiB of LDS.
+constexpr size_t lds_budget(int wg) { return wg >= 1024 ? 80 * 1024 : kLdsBudget; }
+// the wide-frame kernels (mavg_wide.hpp): two workgroups per CU at the longest halos
+constexpr size_t kWideLdsBudget = lds_budget(1024);
+// The debug builds' check of a kernel that carves its own pointers: they are where its layout
+// struct -- what the launcher sized -- puts them, and the layout is within the budget.
+template <typename L>
+__device__ __forceinline__ bool lds_layout_ok(const L& l, const unsigned char* smem, const void* tot, const void* hsum,
+                                              size_t budget) {
+  return smem + l.tot == tot && smem + l.hsum == hsum && l.bytes <= budget;
+}
+
 // ----------------------------------------------------------------------------
 // small helpers
 // ----------------------------------------------------------------------------

@@ -31,6 +31,19 @@ struct DirectParams {
   OutParams o;
 };
 
+// DirectParams::m of a k-frame window
+template <int F>
+constexpr size_t direct_halo_units(int k) { return (size_t)(((long long)k - 1 + F - 1) / F); }
+
+// The dynamic LDS of one workgroup: the stage of m halo units and the tile's U*WG.  Read by the
+// kernel's layout check, launch_direct and launch_direct_block.
+template <typename T, int C, int F, int U, int WG>
+struct DirectLds {
+  size_t bytes;
+  __host__ __device__ constexpr explicit DirectLds(size_t m)
+      : bytes((((m + (size_t)U * WG) * F * C * sizeof(T)) + 15) & ~(size_t)15) {}
+};
+
 template <int OFF, typename A, int F, int C>
 __device__ __forceinline__ void pick_prefix(const A (&pc)[2 * F][C], A (&pre)[F][C]) {
 #pragma unroll
@@ -88,6 +101,7 @@ __global__ __launch_bounds__(WG) void direct_kernel(DirectParams p) {
   const long long t0 = tile * TF;
   const long long h0 = t0 - (long long)m * F;
   MAVG_DCHECK(tile >= 0 && tile < (long long)gridDim.x && t0 < nframes, "direct tile index", tile, gridDim.x);
+  MAVG_DCHECK((DirectLds<T, C, F, U, WG>((size_t)m).bytes <= kLdsBudget), "direct LDS layout", m, U * WG);
   const bool tile_full = (t0 + TF <= nframes);
 
   U_t xr[U];

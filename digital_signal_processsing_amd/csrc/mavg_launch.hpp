@@ -1,5 +1,9 @@
 // mavg_launch.hpp -- host-side launch helpers shared by the libmavg
 // translation units (one TU per kernel family so the build parallelises).
+// A launcher holds no layout arithmetic of its own: a kernel's LDS layout is the *Lds struct
+// beside the kernel, read by the launcher, the dispatch rule and the kernel's debug check against
+// the budgets of mavg_device.hpp; the look-ahead launchers' shared preamble (schedule, grid,
+// workspace layout, the common AheadParams fields) is AheadLaunch below.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -19,10 +23,6 @@ constexpr int kMaxChannels = 8;
 // tile -> XCD mapping of the flat-tile kernels: runs of 64 consecutive tiles
 // per XCD, the 8 XCDs' runs adjacent (remap_tile in mavg_kernels.hpp)
 constexpr int kRemapGroup = 64;
-constexpr size_t kLdsBudget = 64 * 1024;  // per workgroup; keeps >= 2 workgroups per CU
-// A 1024-thread workgroup may take 80 KiB: two of them still fill a CU's 32
-// wave slots within its 160 KiB of LDS.
-constexpr size_t lds_budget(int wg) { return wg >= 1024 ? 80 * 1024 : kLdsBudget; }
 // Work-items (gridDim.x * blockDim.x) of one launch.  The HIP runtime refuses
 // more than 2^32 - 1 in a dimension, however few the workgroups; the kernels
 // that run one thread per sample or per 16 B (naive, the flat copy) cover a
@@ -58,6 +58,17 @@ int raise_dyn_lds_limit(int bytes) {
     return MAVG_ERR_HIP;
   if (cached) set_on[dev].store(bytes, std::memory_order_release);
   return MAVG_OK;
+}
+// One kernel launch with `lds` bytes of dynamic LDS; beyond the default limit the kernel's limit
+// is first raised to its budget on this device.
+template <auto Kernel, typename P>
+int launch_kernel(long long grid, int wg, size_t lds, size_t budget, hipStream_t st, const P& p) {
+  if (lds > 64 * 1024) {
+    const int s = raise_dyn_lds_limit<Kernel>((int)budget);
+    if (s != MAVG_OK) return s;
+  }
+  hipLaunchKernelGGL(Kernel, dim3((unsigned)grid), dim3(wg), lds, st, p);
+  return hipGetLastError() == hipSuccess ? MAVG_OK : MAVG_ERR_HIP;
 }
 
 // Dry-run support for mavg_plan(): when g_plan is set (thread-local), the
@@ -99,8 +110,32 @@ constexpr int block_wg(int block) {
   return wg;
 }
 
+// A kernel's parameter struct (TileParams, WideParams, AheadParams, DirectParams) with the fields
+// they all share set from the view and the window; the rest zero, for the launcher to fill.
+template <typename P>
+P sig_params(const Sig& sg, int k) {
+  P p{};
+  p.in = sg.in;
+  p.out = sg.out;
+  p.hist = sg.hist;
+  p.nframes = sg.nframes;
+  p.pre = sg.pre;
+  p.k = k;
+  p.o = make_out_params(k);
+  return p;
+}
+
+// f(std::integral_constant<int, V>) for the V among Vs that equals v; `none` where none does
+template <int... Vs, typename Fn>
+int dispatch_int(int v, int none, Fn&& f) {
+  int r = none;
+  (void)((v == Vs && ((r = f(std::integral_constant<int, Vs>{})), true)) || ...);
+  return r;
+}
+constexpr int kNoFit = -1;  // inside a dispatch_int: the geometry does not fit (no mavg_status)
+
 // family entry points (defined in mavg_scan_*.hip / mavg_direct.hip)
-// Workspace: the look-ahead scan needs its record granules (ahead_granule_bytes)
+// Workspace: the look-ahead scan needs its record granules (AheadLaunch::need)
 // in caller-owned device memory (zeroed on the stream before each launch);
 // every other launch needs none.
 struct Workspace {
@@ -154,6 +189,16 @@ bool ragged_scan_fits(int dtype, int C, size_t max_row_frames, int grade);
 // MAVG_ERR_UNSUPPORTED: the halo does not fit, or the launch would exceed grid_too_large
 int ragged_scan_any(int dtype, int C, const RaggedSig& rs, int grade, hipStream_t st);
 
+// ceil(k / F): the units a k-frame halo takes (TileParams / AheadParams halo_units)
+template <int F>
+constexpr size_t tile_halo_units(int k) { return (size_t)(((long long)k + F - 1) / F); }
+// Whether the tile scan's layout for a k-frame halo fits its workgroup's LDS budget: the
+// launcher's check, asked ahead by the dispatch rules.
+template <typename T, typename A, int C, int F, int U, int WG = kWG>
+bool tile_fits(int k) {
+  return TileLds<T, A, C, F, U, WG>(tile_halo_units<F>(k)).bytes <= lds_budget(WG);
+}
+
 // flat-tile scan: one workgroup per tile, carry rebuilt from the k-frame halo
 // DV: the int16 output division of the tile scan -- the magic multiply, which
 // measured faster than the fp64 product here (int16 stereo k=1024: 0.779 vs
@@ -163,26 +208,15 @@ template <typename T, typename A, int C, int F, int U, bool HS, int NT = kNtLoad
           bool RC = true, int DV = (sizeof(T) == 2 ? 1 : 0), bool DMA = false>
 int launch_tile_scan(const Sig& sg, int k, hipStream_t st, int xcd_remap = kRemapGroup) {
   constexpr int TF = WG * F * U;
-  constexpr int NSEG = U * (WG / 64);
   constexpr int VE = F * C;
-  const long long nframes = sg.nframes;
-  TileParams p{};
-  p.in = sg.in;
-  p.out = sg.out;
-  p.hist = sg.hist;
-  p.nframes = nframes;
-  p.pre = sg.pre;
+  TileParams p = sig_params<TileParams>(sg, k);
   p.eio = sg.eio;
-  p.k = k;
-  p.o = make_out_params(k);
-  p.halo_units = (k + F - 1) / F;
+  p.halo_units = (int)tile_halo_units<F>(k);
   p.xk_off = (int)((VE - ((long long)k * C) % VE) % VE);
   p.xcd_remap = xcd_remap;
-  p.ntiles = (nframes + TF - 1) / TF;
-  const size_t stage = (((size_t)(p.halo_units + U * WG + 1) * VE * sizeof(T)) + 15) & ~(size_t)15;
-  const size_t lds = stage + (size_t)(NSEG + WG / 64) * C * sizeof(A);
-  if (lds > lds_budget(WG)) return MAVG_ERR_UNSUPPORTED;
-  if (grid_too_large(p.ntiles, WG)) return MAVG_ERR_UNSUPPORTED;
+  p.ntiles = (sg.nframes + TF - 1) / TF;
+  const size_t lds = TileLds<T, A, C, F, U, WG>(tile_halo_units<F>(k)).bytes;
+  if (lds > lds_budget(WG) || grid_too_large(p.ntiles, WG)) return MAVG_ERR_UNSUPPORTED;
   if (g_plan) {
     snprintf(g_plan->text, sizeof(g_plan->text),
              "tile_scan<%s,acc=%s,C=%d,F=%d,U=%d,%s,nt=%d,rc=%d,dv=%d,dma=%d> grid=%lld block=%d lds=%zu "
@@ -191,13 +225,7 @@ int launch_tile_scan(const Sig& sg, int k, hipStream_t st, int xcd_remap = kRema
              p.ntiles, WG, lds, TF, xcd_remap);
     return MAVG_OK;
   }
-  if (lds > 64 * 1024) {  // beyond the default dynamic-LDS limit: raise it on this device
-    const int st = raise_dyn_lds_limit<&tile_scan_kernel<T, A, C, F, U, HS, NT, WG, RC, DV, DMA>>((int)lds_budget(WG));
-    if (st != MAVG_OK) return st;
-  }
-  hipLaunchKernelGGL((tile_scan_kernel<T, A, C, F, U, HS, NT, WG, RC, DV, DMA>), dim3((unsigned)p.ntiles), dim3(WG), lds, st,
-                     p);
-  return hipGetLastError() == hipSuccess ? MAVG_OK : MAVG_ERR_HIP;
+  return launch_kernel<&tile_scan_kernel<T, A, C, F, U, HS, NT, WG, RC, DV, DMA>>(p.ntiles, WG, lds, lds_budget(WG), st, p);
 }
 
 // wide-frame tile scan (mavg_wide.hpp): lanes own chunks of P consecutive
@@ -205,42 +233,25 @@ int launch_tile_scan(const Sig& sg, int k, hipStream_t st, int xcd_remap = kRema
 // (the host's vector path), halo + tile staged in a swizzled LDS stage.
 template <typename T, typename A, int C, int P, int U, int WG, int NT, int DV = 0>
 int launch_wide_tile(const Sig& sg, int k, hipStream_t st, int xcd_remap = kRemapGroup) {
+  using Lds = WideTileLds<T, A, C, P, U, WG>;
   constexpr int EPG = 16 / (int)sizeof(T);
-  constexpr int G = P * C / EPG;
-  constexpr int TF = WG * P * U;
-  constexpr int TG = WG * U * G;
-  constexpr int NSEG = U * (WG / 64);
-  const long long nframes = sg.nframes;
-  const long long hg = ((long long)k * C + EPG - 1) / EPG;  // granules covering the k-frame halo
-  const long long Hg = (hg + 15) / 16 * 16;                // whole 256-B LDS rows
-  const size_t lds = (size_t)(Hg + TG) * 16 + (size_t)(NSEG + WG / 64) * C * sizeof(A);
-  if (lds > 80 * 1024) return MAVG_ERR_UNSUPPORTED;  // two workgroups per CU at the longest halos
-  const long long ntiles = (nframes + TF - 1) / TF;
-  if (grid_too_large(ntiles, WG)) return MAVG_ERR_UNSUPPORTED;
+  constexpr int TF = Lds::TF;
+  const long long Hg = wide_halo_granules<T, C>(k);
+  const size_t lds = Lds((size_t)Hg).bytes;
+  const long long ntiles = (sg.nframes + TF - 1) / TF;
+  if (lds > kWideLdsBudget || grid_too_large(ntiles, WG)) return MAVG_ERR_UNSUPPORTED;
   if (g_plan) {
     snprintf(g_plan->text, sizeof(g_plan->text),
              "wide_tile<%s,acc=%s,C=%d,P=%d,U=%d,nt=%d,dv=%d> grid=%lld block=%d lds=%zu tile_frames=%d remap=%d",
              type_name<T>(), type_name<A>(), C, P, U, NT, DV, ntiles, WG, lds, TF, xcd_remap);
     return MAVG_OK;
   }
-  WideParams p{};
-  p.in = sg.in;
-  p.out = sg.out;
-  p.hist = sg.hist;
-  p.nframes = nframes;
+  WideParams p = sig_params<WideParams>(sg, k);
   p.ntiles = ntiles;
-  p.k = k;
   p.halo_g = (int)Hg;
   p.xk_off = (int)((EPG - ((long long)k * C) % EPG) % EPG);
   p.xcd_remap = xcd_remap;
-  p.pre = sg.pre;
-  p.o = make_out_params(k);
-  if (lds > 64 * 1024) {
-    const int s = raise_dyn_lds_limit<&wide_tile_kernel<T, A, C, P, U, WG, NT, DV>>(80 * 1024);
-    if (s != MAVG_OK) return s;
-  }
-  hipLaunchKernelGGL((wide_tile_kernel<T, A, C, P, U, WG, NT, DV>), dim3((unsigned)ntiles), dim3(WG), lds, st, p);
-  return hipGetLastError() == hipSuccess ? MAVG_OK : MAVG_ERR_HIP;
+  return launch_kernel<&wide_tile_kernel<T, A, C, P, U, WG, NT, DV>>(ntiles, WG, lds, kWideLdsBudget, st, p);
 }
 
 // the channel-per-lane tile (mavg_wide.hpp chan_tile_kernel): lanes own one
@@ -253,60 +264,35 @@ int launch_wide_tile(const Sig& sg, int k, hipStream_t st, int xcd_remap = kRema
 template <typename T, typename A, int C, int Q, int WG, int NT, int DV = 0, bool XG = false, bool IPOK = false,
           int XL = 0>
 int launch_chan_tile(const Sig& sg, int k, hipStream_t st, int xcd_remap = kRemapGroup) {
+  using Lds = ChanTileLds<T, A, C, Q, WG, XG>;
   constexpr int EPG = 16 / (int)sizeof(T);
-  constexpr int NW = WG / 64;
-  constexpr int CL = C * (int)sizeof(T) / 4;  // dword columns per frame (a lane's)
-  constexpr int TF = NW * (64 / CL) * Q;      // waves x frame blocks x frames per block
-  constexpr int TG = TF * C / EPG;
-  const long long nframes = sg.nframes;
-  const long long hg = ((long long)k * C + EPG - 1) / EPG;  // granules covering the k-frame halo
-  const long long Hg = (hg + 15) / 16 * 16;                // whole 256-B LDS rows
+  constexpr int TF = Lds::TF;
+  const long long Hg = wide_halo_granules<T, C>(k);
   if (XG && (long long)k < TF) return MAVG_ERR_UNSUPPORTED;  // x[n-k] must lie in the halo
-  const size_t lds = (size_t)(Hg + (XG ? 0 : TG)) * 16 + (size_t)2 * NW * C * sizeof(A);
-  if (lds > 80 * 1024) return MAVG_ERR_UNSUPPORTED;
-  const long long ntiles = (nframes + TF - 1) / TF;
-  if (grid_too_large(ntiles, WG)) return MAVG_ERR_UNSUPPORTED;
+  const size_t lds = Lds((size_t)Hg).bytes;
+  const long long ntiles = (sg.nframes + TF - 1) / TF;
+  if (lds > kWideLdsBudget || grid_too_large(ntiles, WG)) return MAVG_ERR_UNSUPPORTED;
   const bool ip = XG && IPOK && Hg * EPG == (long long)k * C;  // staged halo frames Hg EPG / C == k
   if (g_plan) {
     snprintf(g_plan->text, sizeof(g_plan->text),
              "chan_tile<%s,acc=%s,C=%d,Q=%d,nt=%d,dv=%d%s%s%s> grid=%lld block=%d lds=%zu tile_frames=%d remap=%d",
              type_name<T>(), type_name<A>(), C, Q, NT, DV, XG ? ",xg=1" : "", ip ? ",ip=1" : "", XL ? ",xl=1" : "",
-             ntiles, WG, lds, TF,
-             xcd_remap);
+             ntiles, WG, lds, TF, xcd_remap);
     return MAVG_OK;
   }
-  WideParams p{};
-  p.in = sg.in;
-  p.out = sg.out;
-  p.hist = sg.hist;
-  p.nframes = nframes;
+  WideParams p = sig_params<WideParams>(sg, k);
   p.ntiles = ntiles;
-  p.k = k;
-  p.halo_g = (int)Hg;
-  p.xk_off = 0;
+  p.halo_g = (int)Hg;  // (xk_off 0: whole frames per granule)
   p.xcd_remap = xcd_remap;
-  p.pre = sg.pre;
-  p.o = make_out_params(k);
-  auto launch = [&](auto ipc) -> int {
-    constexpr bool IP = decltype(ipc)::value;
-    if (lds > 64 * 1024) {
-      const int s = raise_dyn_lds_limit<&chan_tile_kernel<T, A, C, Q, WG, NT, DV, XG, IP, XL>>(80 * 1024);
-      if (s != MAVG_OK) return s;
-    }
-    hipLaunchKernelGGL((chan_tile_kernel<T, A, C, Q, WG, NT, DV, XG, IP, XL>), dim3((unsigned)ntiles), dim3(WG), lds, st, p);
-    return hipGetLastError() == hipSuccess ? MAVG_OK : MAVG_ERR_HIP;
-  };
   if constexpr (XG && IPOK) {
-    if (ip) return launch(std::true_type{});
+    if (ip) return launch_kernel<&chan_tile_kernel<T, A, C, Q, WG, NT, DV, XG, true, XL>>(ntiles, WG, lds, kWideLdsBudget, st, p);
   }
-  return launch(std::false_type{});
+  return launch_kernel<&chan_tile_kernel<T, A, C, Q, WG, NT, DV, XG, false, XL>>(ntiles, WG, lds, kWideLdsBudget, st, p);
 }
 
 // look-ahead scan (one pass over HBM): zero the record granules, then one
 // launch whose tile t publishes the records of tile t + ahead and scans
-// tile t with its carry from earlier records (mavg_lookback.hpp).
-// Workspace: the granule block, at the start of the workspace, padded to
-// 16 bytes (the memset's fast form, cdna_hip_programming.md Guideline 16).
+// tile t with its carry from earlier records (mavg_lookback.hpp); the workspace: AheadLaunch.
 constexpr int kAheadSpin = 256;   // polls of an untagged granule before recomputing it
 // Test hook (mavg_test_ahead_schedule, include/mavg_debug.h; compiled into
 // the debug build only, MAVG_TEST_HOOKS): the parity tests force the
@@ -318,12 +304,6 @@ constexpr int kAheadSpin = 256;   // polls of an untagged granule before recompu
 extern std::atomic<int> g_test_ahead_slots;
 extern std::atomic<int> g_test_ahead_spin;
 #endif
-template <typename T, typename A, int C, int F, int U>
-constexpr size_t ahead_granule_bytes(long long nrec) {
-  using SA = typename ScanAcc<T, A>::type;
-  // + 16 bytes of launch statistics (MAVG_AHEAD_STATS builds only)
-  return (((size_t)(nrec > 0 ? nrec : 1) * C * GranCount<SA>::n * 8) + 15) / 16 * 16 + 16;
-}
 // Windows past an XCD's L2 reach (ahead_scan_kernel): window-matched runs,
 // remap mode G.  The window is m = k/T tiles; with runs of G tiles a period
 // is 8G, and x[n-k]'s tile lies J periods back on the tile's own XCD when
@@ -373,103 +353,118 @@ inline bool agg_first_range(long long k) {
   return false;
 }
 
+// The launch preamble the look-ahead launchers share (launch_ahead_scan, launch_wide_ahead;
+// tools/tune/pair_ahead.hpp).  make() sets the schedule, the grid and the workspace layout: the
+// records, the run totals, 16 bytes of launch statistics (MAVG_AHEAD_STATS builds only), the
+// tuning builds' trace, each padded to 16 bytes (the memset's fast form, cdna_hip_programming.md
+// Guideline 16).  begin() checks and zeroes the caller's workspace and fills the AheadParams
+// fields every look-ahead kernel takes.  The launcher checks its LDS and answers plan mode between
+// the two: UNSUPPORTED (grid, then LDS), plan mode's return, WORKSPACE, MISALIGNED, HIP.
+struct AheadLaunch {
+  int TF;          // tile frames
+  int ahead;       // D, a multiple of 8 (the test hook's, where set)
+  int spin;
+  int xcd_remap;   // 1, or the run length G past the L2 reach
+  long long ntiles, nfull;
+  long long runs_done;  // runs [0, runs_done) get a published total
+  size_t rec_bytes, trace_bytes, need;
+
+  // rec_per_tile: records per whole tile (one, or one per wave); runs: with run totals
+  template <typename T, typename A, int C>
+  int make(const Sig& sg, int k, int ahead_slots, int tile_frames, int WG, int rec_per_tile, bool runs) {
+    TF = tile_frames;
+    ahead = ahead_slots & ~7;
+    // the tuned D sets the run length G below; the test hook changes only the
+    // producer distance, so a forced schedule keeps the plan's tile -> XCD
+    // mapping and run-total grouping (the same decomposition, the same bits)
+    const int ahead_plan = ahead;
+    spin = kAheadSpin;
+#ifdef MAVG_TEST_HOOKS
+    if (const int t = g_test_ahead_slots.load(std::memory_order_relaxed); t >= 0) ahead = t & ~7;
+    if (const int t = g_test_ahead_spin.load(std::memory_order_relaxed); t >= 0) spin = t;
+#endif
+    // one contiguous run per XCD (remap mode 1: x[n-k] is then an L2 hit of the
+    // same XCD) while the window's bytes fit comfortably in an XCD's 4 MB L2;
+    // past that, 8 separate runs would fetch x[n-k] from the MALL: window-
+    // matched runs (ahead_run_length), the chip streaming one front, no head duty.
+    // Measured, 2^30 fp32 (profiles/r03_tuning/remap/, period/): one run per
+    // XCD -> runs of 64 tiles -> window-matched runs: k=4e6 0.185 -> 0.526;
+    // k=1e6 0.524 -> 0.588 -> 0.668; k=6e5 0.594 -> 0.599 -> 0.681
+    xcd_remap = ahead_past_l2(k, C, sizeof(T), TF) ? ahead_run_length(k, TF, ahead_plan) : 1;
+    ntiles = (sg.nframes + TF - 1) / TF;
+    nfull = sg.nframes / TF;
+    if (grid_too_large(ntiles, WG)) return MAVG_ERR_UNSUPPORTED;
+    // runs with a published total: run r's is published with the record of
+    // the last tile of run r + 8, which must be a whole tile of a complete
+    // period (remap_tile maps the blocks past those to themselves)
+    const long long P = runs && xcd_remap > 1 ? ntiles / (8LL * xcd_remap) : 0;
+    const long long pub_periods = P - 1 - (8LL * xcd_remap * P > nfull ? 1 : 0);
+    runs_done = pub_periods > 0 ? 8 * pub_periods : 0;
+    using SA = typename ScanAcc<T, A>::type;
+    rec_bytes = (((size_t)std::max(nfull * rec_per_tile, 1LL) * C * GranCount<SA>::n * 8) + 15) / 16 * 16;
+    const size_t run_bytes = ((size_t)runs_done * C * GranCount<A>::n * 8 + 15) / 16 * 16;
+#ifdef MAVG_AHEAD_TRACE
+    trace_bytes = (size_t)ntiles * 64;  // tuning builds: 8 stamps per tile, after the stats
+#else
+    trace_bytes = 0;
+#endif
+    need = rec_bytes + run_bytes + 16 + trace_bytes;
+    return MAVG_OK;
+  }
+
+  // the caller sets halo_units, xk_off and eio, and launches
+  int begin(AheadParams& p, const Sig& sg, int k, bool self, Workspace ws, hipStream_t st) const {
+    if (ws.ptr == nullptr || ws.bytes < need) return MAVG_ERR_WORKSPACE;
+    if ((reinterpret_cast<uintptr_t>(ws.ptr) & 15u) != 0) return MAVG_ERR_MISALIGNED;
+    if (hipMemsetAsync(ws.ptr, 0, need, st) != hipSuccess) return MAVG_ERR_HIP;
+    unsigned char* base = static_cast<unsigned char*>(ws.ptr);
+    p = sig_params<AheadParams>(sg, k);
+    p.nfull = nfull;
+    p.xcd_remap = xcd_remap;
+    p.runs_done = runs_done;
+    p.ahead = ahead;
+    p.head = xcd_remap == 1 ? (int)std::min<long long>((long long)k / TF, nfull) : 0;  // head duty: mode 1 only
+    p.spin = spin;
+    p.self = self ? 1 : 0;
+    p.gran = reinterpret_cast<unsigned long long*>(base);
+    p.runs = reinterpret_cast<unsigned long long*>(base + rec_bytes);
+    p.stats = base + need - trace_bytes - 16;
+#ifdef MAVG_AHEAD_TRACE
+    p.trace = reinterpret_cast<unsigned long long*>(base + need - trace_bytes);
+#endif
+    return MAVG_OK;
+  }
+};
+
 template <typename T, typename A, int C, int F, int U, int NT, bool RC, bool DMA, bool WREC, int DV = 0, bool HS = false,
           bool RUNS = false, int WG = kWG>
 // lds_floor: the LDS the launch allocates at least (fewer workgroups per CU, a footprint cap; 0: none)
 int launch_ahead_scan(const Sig& sg, int k, hipStream_t st, Workspace ws, int ahead, bool self = false,
                       size_t lds_floor = 0) {
-  constexpr int NW = WG / 64;
-  const long long nframes = sg.nframes;
-  ahead &= ~7;
-  // the tuned D sets the run length G below; the test hook changes only the
-  // producer distance, so a forced schedule keeps the plan's tile -> XCD
-  // mapping and run-total grouping (the same decomposition, the same bits)
-  const int ahead_plan = ahead;
-  int spin = kAheadSpin;
-#ifdef MAVG_TEST_HOOKS
-  {
-    const int t = g_test_ahead_slots.load(std::memory_order_relaxed);
-    if (t >= 0) ahead = t & ~7;
-  }
-  {
-    const int t = g_test_ahead_spin.load(std::memory_order_relaxed);
-    if (t >= 0) spin = t;
-  }
-#endif
-  // one contiguous run per XCD (remap mode 1: x[n-k] is then an L2 hit of the
-  // same XCD) while the window's bytes fit comfortably in an XCD's 4 MB L2;
-  // past that, 8 separate runs would fetch x[n-k] from the MALL: window-
-  // matched runs (ahead_run_length), the chip streaming one front, no head duty.
-  // Measured, 2^30 fp32 (profiles/r03_tuning/remap/, period/): one run per
-  // XCD -> runs of 64 tiles -> window-matched runs: k=4e6 0.185 -> 0.526;
-  // k=1e6 0.524 -> 0.588 -> 0.668; k=6e5 0.594 -> 0.599 -> 0.681
   constexpr int TF = WG * F * U;
-  const int xcd_remap = ahead_past_l2(k, C, sizeof(T), TF) ? ahead_run_length(k, TF, ahead_plan) : 1;
-  if (RUNS && xcd_remap == 1) return MAVG_ERR_UNSUPPORTED;
   constexpr int VE = F * C;
-  constexpr int NSEG = U * NW;
-  using SA = typename ScanAcc<T, A>::type;
-  constexpr size_t kStageBytes = (((size_t)(U * WG + 1) * VE * sizeof(T)) + 15) & ~(size_t)15;
-  const long long ntiles = (nframes + TF - 1) / TF;
-  const long long nfull = nframes / TF;
-  if (grid_too_large(ntiles, WG)) return MAVG_ERR_UNSUPPORTED;
-  // runs with a published total: run r's is published with the record of
-  // the last tile of run r + 8, which must be a whole tile of a complete
-  // period (remap_tile maps the blocks past those to themselves)
-  const long long P = xcd_remap > 1 ? ntiles / (8LL * xcd_remap) : 0;
-  const long long pub_periods = P - 1 - (8LL * xcd_remap * P > nfull ? 1 : 0);
-  const long long runs_done = RUNS && pub_periods > 0 ? 8 * pub_periods : 0;
-  const size_t rec_bytes = ahead_granule_bytes<T, A, C, F, U>(nfull * (WREC ? NW : 1)) - 16;
-  const size_t run_bytes = ((size_t)runs_done * C * GranCount<A>::n * 8 + 15) / 16 * 16;
-#ifdef MAVG_AHEAD_TRACE
-  const size_t trace_bytes = (size_t)ntiles * 64;  // tuning builds: 8 stamps per tile, after the stats
-#else
-  const size_t trace_bytes = 0;
-#endif
-  const size_t need = rec_bytes + run_bytes + 16 + trace_bytes;
-  size_t lds = kStageBytes + (size_t)NW * C * sizeof(A) + (size_t)(NSEG + 3 * NW) * C * sizeof(SA);
-  if (HS) lds = (lds + 15) / 16 * 16 + (size_t)U * WG * VE * sizeof(T);  // + the tile
-  if (lds > kLdsBudget) return MAVG_ERR_UNSUPPORTED;
-  lds = std::max(lds, lds_floor);
+  AheadLaunch g;
+  const int gs = g.make<T, A, C>(sg, k, ahead, TF, WG, WREC ? WG / 64 : 1, RUNS);
+  if (gs != MAVG_OK) return gs;
+  using Lds = AheadLds<T, A, C, F, U, WG, HS>;
+  if ((RUNS && g.xcd_remap == 1) || Lds::bytes > kLdsBudget) return MAVG_ERR_UNSUPPORTED;
+  const size_t lds = std::max((size_t)Lds::bytes, lds_floor);
   if (g_plan) {
     snprintf(g_plan->text, sizeof(g_plan->text),
              "ahead_scan<%s,acc=%s,C=%d,F=%d,U=%d,%s,nt=%d,rc=%d,dma=%d,wrec=%d,dv=%d> grid=%lld block=%d lds=%zu "
              "tile_frames=%d ahead=%d remap=%d%s%s ws=%zu",
              type_name<T>(), type_name<A>(), C, F, U, HS ? "hillis" : "blelloch", NT, (int)RC, (int)DMA, (int)WREC, DV,
-             ntiles, WG, lds, TF, ahead, xcd_remap, RUNS ? " runs=1" : "", self ? " self=1" : "", need);
-    g_plan->ws_bytes = need;
+             g.ntiles, WG, lds, TF, g.ahead, g.xcd_remap, RUNS ? " runs=1" : "", self ? " self=1" : "", g.need);
+    g_plan->ws_bytes = g.need;
     return MAVG_OK;
   }
-  if (ws.ptr == nullptr || ws.bytes < need) return MAVG_ERR_WORKSPACE;
-  if ((reinterpret_cast<uintptr_t>(ws.ptr) & 15u) != 0) return MAVG_ERR_MISALIGNED;
-  if (hipMemsetAsync(ws.ptr, 0, need, st) != hipSuccess) return MAVG_ERR_HIP;
-  AheadParams p{};
-  p.in = sg.in;
-  p.out = sg.out;
-  p.hist = sg.hist;
-  p.nframes = nframes;
-  p.pre = sg.pre;
+  AheadParams p;
+  const int s = g.begin(p, sg, k, self, ws, st);
+  if (s != MAVG_OK) return s;
   p.eio = sg.eio;
-  p.nfull = nfull;
-  p.k = k;
-  p.o = make_out_params(k);
-  p.halo_units = (k + F - 1) / F;
+  p.halo_units = (int)tile_halo_units<F>(k);
   p.xk_off = (int)((VE - ((long long)k * C) % VE) % VE);
-  p.xcd_remap = xcd_remap;
-  p.runs_done = runs_done;
-  p.ahead = ahead;
-  p.head = xcd_remap == 1 ? (int)std::min<long long>((long long)k / TF, nfull) : 0;  // head duty: mode 1 only
-  p.spin = spin;
-  p.self = self ? 1 : 0;
-  p.gran = static_cast<unsigned long long*>(ws.ptr);
-  p.runs = reinterpret_cast<unsigned long long*>(static_cast<unsigned char*>(ws.ptr) + rec_bytes);
-  p.stats = static_cast<unsigned char*>(ws.ptr) + need - trace_bytes - 16;
-#ifdef MAVG_AHEAD_TRACE
-  p.trace = reinterpret_cast<unsigned long long*>(static_cast<unsigned char*>(ws.ptr) + need - trace_bytes);
-#endif
-  hipLaunchKernelGGL((ahead_scan_kernel<T, A, C, F, U, NT, RC, DMA, WREC, DV, HS, RUNS, WG>), dim3((unsigned)ntiles),
-                     dim3(WG), lds, st, p);
-  return hipGetLastError() == hipSuccess ? MAVG_OK : MAVG_ERR_HIP;
+  return launch_kernel<&ahead_scan_kernel<T, A, C, F, U, NT, RC, DMA, WREC, DV, HS, RUNS, WG>>(g.ntiles, WG, lds, kLdsBudget, st, p);
 }
 
 // The look-ahead scan's shape for the dtype, channel count and window
@@ -596,84 +591,30 @@ int launch_wide_ahead(const Sig& sg, int k, hipStream_t st, Workspace ws, int ah
   // (self + XL: the self-published record would be summed before the quad transposes)
   if (self && !(CH && XG && XL != 1)) return MAVG_ERR_UNSUPPORTED;
   if (XL == 2 && !self) return MAVG_ERR_UNSUPPORTED;  // XL = 2: the columns formed before the self-published record
-  constexpr int NW = WG / 64;
+  using Lds = WideAheadLds<T, A, C, P, UW, WG, CH, XG>;
   constexpr int EPG = 16 / (int)sizeof(T);
-  constexpr int CL = C * (int)sizeof(T) / 4 > 0 ? C * (int)sizeof(T) / 4 : 1;  // CH: dword columns per frame
-  constexpr int TF = CH ? NW * (64 / CL) * P : WG * P * UW;  // CH: P frames of one dword column per lane
-  constexpr int TG = TF * C / EPG;
-  constexpr int NSEG = UW * NW;
-  using SA = typename ScanAcc<T, A>::type;
-  const long long nframes = sg.nframes;
-  ahead &= ~7;
-  const int ahead_plan = ahead;
-  int spin = kAheadSpin;
-#ifdef MAVG_TEST_HOOKS
-  {
-    const int t = g_test_ahead_slots.load(std::memory_order_relaxed);
-    if (t >= 0) ahead = t & ~7;
-  }
-  {
-    const int t = g_test_ahead_spin.load(std::memory_order_relaxed);
-    if (t >= 0) spin = t;
-  }
-#endif
-  const int xcd_remap = ahead_past_l2(k, C, sizeof(T), TF) ? ahead_run_length(k, TF, ahead_plan) : 1;
-  const long long ntiles = (nframes + TF - 1) / TF;
-  const long long nfull = nframes / TF;
-  if (grid_too_large(ntiles, WG)) return MAVG_ERR_UNSUPPORTED;
-#ifdef MAVG_AHEAD_TRACE
-  const size_t trace_bytes = (size_t)ntiles * 64;  // tuning builds: 8 stamps per tile, after the stats
-#else
-  const size_t trace_bytes = 0;
-#endif
-  const size_t need = ahead_granule_bytes<T, A, C, F, U>(nfull) + trace_bytes;  // per-tile records + 16
-  // the shifted tile (+ one granule for an x[n-k] extraction) and, unless XG, the tile
-  const size_t lds = (size_t)((XG ? 1 : 2) * TG + 1) * 16 + (size_t)NW * C * sizeof(A) +
-                     (size_t)(NSEG + 3 * NW) * C * sizeof(SA);
-  if (lds > 80 * 1024) return MAVG_ERR_UNSUPPORTED;
+  constexpr int TF = Lds::TF;
+  AheadLaunch g;
+  const int gs = g.make<T, A, C>(sg, k, ahead, TF, WG, 1, false);  // per-tile records, no run totals
+  if (gs != MAVG_OK) return gs;
+  constexpr size_t lds = Lds::bytes;
+  if (lds > kWideLdsBudget) return MAVG_ERR_UNSUPPORTED;
   if (g_plan) {
     snprintf(g_plan->text, sizeof(g_plan->text),
              "wide_ahead<%s,acc=%s,C=%d,P=%d,U=%d,nt=%d,dv=%d,F=%d,FU=%d%s%s,mw=%d,xl=%d> grid=%lld block=%d lds=%zu "
              "tile_frames=%d ahead=%d remap=%d%s ws=%zu",
-             type_name<T>(), type_name<A>(), C, P, UW, NT, DV, F, U, CH ? ",ch=1" : "", XG ? ",xg=1" : "", MW, XL, ntiles,
-             WG, lds, TF, ahead, xcd_remap, self ? " self=1" : "", need);
-    g_plan->ws_bytes = need;
+             type_name<T>(), type_name<A>(), C, P, UW, NT, DV, F, U, CH ? ",ch=1" : "", XG ? ",xg=1" : "", MW, XL, g.ntiles,
+             WG, lds, TF, g.ahead, g.xcd_remap, self ? " self=1" : "", g.need);
+    g_plan->ws_bytes = g.need;
     return MAVG_OK;
   }
-  if (ws.ptr == nullptr || ws.bytes < need) return MAVG_ERR_WORKSPACE;
-  if ((reinterpret_cast<uintptr_t>(ws.ptr) & 15u) != 0) return MAVG_ERR_MISALIGNED;
-  if (hipMemsetAsync(ws.ptr, 0, need, st) != hipSuccess) return MAVG_ERR_HIP;
-  AheadParams p{};
-  p.in = sg.in;
-  p.out = sg.out;
-  p.hist = sg.hist;
-  p.nframes = nframes;
-  p.pre = sg.pre;
+  AheadParams p;
+  const int s = g.begin(p, sg, k, self, ws, st);
+  if (s != MAVG_OK) return s;
   p.eio = 0;
-  p.nfull = nfull;
-  p.k = k;
-  p.o = make_out_params(k);
-  p.halo_units = (k + F - 1) / F;
+  p.halo_units = (int)tile_halo_units<F>(k);
   p.xk_off = (((F - k % F) % F) * C) % EPG;
-  p.xcd_remap = xcd_remap;
-  p.runs_done = 0;
-  p.ahead = ahead;
-  p.head = xcd_remap == 1 ? (int)std::min<long long>((long long)k / TF, nfull) : 0;
-  p.spin = spin;
-  p.self = self ? 1 : 0;
-  p.gran = static_cast<unsigned long long*>(ws.ptr);
-  p.runs = nullptr;
-  p.stats = static_cast<unsigned char*>(ws.ptr) + need - trace_bytes - 16;
-#ifdef MAVG_AHEAD_TRACE
-  p.trace = reinterpret_cast<unsigned long long*>(static_cast<unsigned char*>(ws.ptr) + need - trace_bytes);
-#endif
-  if (lds > 64 * 1024) {
-    const int s = raise_dyn_lds_limit<&wide_ahead_kernel<T, A, C, P, UW, WG, NT, DV, F, U, CH, XG, MW, XL>>(80 * 1024);
-    if (s != MAVG_OK) return s;
-  }
-  hipLaunchKernelGGL((wide_ahead_kernel<T, A, C, P, UW, WG, NT, DV, F, U, CH, XG, MW, XL>), dim3((unsigned)ntiles), dim3(WG), lds,
-                     st, p);
-  return hipGetLastError() == hipSuccess ? MAVG_OK : MAVG_ERR_HIP;
+  return launch_kernel<&wide_ahead_kernel<T, A, C, P, UW, WG, NT, DV, F, U, CH, XG, MW, XL>>(g.ntiles, WG, lds, kWideLdsBudget, st, p);
 }
 
 // Algorithm selection for the scan family (measured on MI355X with
@@ -695,12 +636,6 @@ int dispatch_scan_f(const Sig& sg, int k, int block, hipStream_t st, Workspace w
   constexpr int VE = F * C;
   constexpr int kUnitBytes = VE * (int)sizeof(T);
   const long long halo_bytes = (long long)k * C * (long long)sizeof(T);
-  auto tile_lds = [&](int U, int WG = kWG) -> long long {
-    const long long hu = (k + F - 1) / F;
-    return (hu + (long long)U * WG + 1) * kUnitBytes + (U * (WG / 64) + WG / 64) * C * (long long)sizeof(A);
-  };
-  auto fits = [&](int U, int WG) { return tile_lds(U, WG) <= (long long)lds_budget(WG); };
-  constexpr long long kB = (long long)kLdsBudget;
   constexpr int kNt = kNtLoad | kNtStore;
   // split policy: nt tile loads except the tail the next tile's halo re-reads,
   // nt halo loads (their last use), nt stores (tools/tune/sweep_nt.sh: +1-4 %
@@ -710,20 +645,19 @@ int dispatch_scan_f(const Sig& sg, int k, int block, hipStream_t st, Workspace w
     // the reference's block size: a U=2 tile of block_wg(block) threads while
     // its halo fits that workgroup's LDS, else the tuned dispatch below (the
     // plan string shows the workgroup that runs)
-    const int wg = block_wg(block);
     constexpr bool kR = sizeof(T) == 4;  // RC as in the tuned rules (fp32 on, int16 off)
-    if (wg == 64 && fits(2, 64)) return launch_tile_scan<T, A, C, F, 2, HS, kNtS, 64, kR>(sg, k, st);
-    if (wg == 128 && fits(2, 128)) return launch_tile_scan<T, A, C, F, 2, HS, kNtS, 128, kR>(sg, k, st);
-    if (wg == 256 && fits(2, 256)) return launch_tile_scan<T, A, C, F, 2, HS, kNtS, 256, kR>(sg, k, st);
-    if (wg == 512 && fits(2, 512)) return launch_tile_scan<T, A, C, F, 2, HS, kNtS, 512, kR>(sg, k, st);
-    if (wg == 1024 && fits(2, 1024)) return launch_tile_scan<T, A, C, F, 2, HS, kNtS, 1024, kR>(sg, k, st);
+    const int s = dispatch_int<64, 128, 256, 512, 1024>(block_wg(block), kNoFit, [&](auto wg) {
+      constexpr int WG = decltype(wg)::value;
+      return tile_fits<T, A, C, F, 2, WG>(k) ? launch_tile_scan<T, A, C, F, 2, HS, kNtS, WG, kR>(sg, k, st) : kNoFit;
+    });
+    if (s != kNoFit) return s;
   }
   if constexpr (!HS && sizeof(T) == 4 && C == 4 && F == 2) {
     // fp32 4 channels in 32-B units (dispatch_scan_c): 1024-frame tiles up to
     // 4 KiB of halo, then the look-ahead scan in 1024-frame tiles (in-process
     // A/B against 1-frame units, profiles/r03_tuning/c4/: k=7 0.46 -> 0.64,
     // k=200 0.45 -> 0.65, k=2000 0.41 -> 0.50, k=44100 0.40 -> 0.48)
-    if (halo_bytes <= 4096 && fits(2, kWG)) return launch_tile_scan<T, A, C, F, 2, false, kNtS, kWG, true>(sg, k, st);
+    if (halo_bytes <= 4096 && tile_fits<T, A, C, F, 2, kWG>(k)) return launch_tile_scan<T, A, C, F, 2, false, kNtS, kWG, true>(sg, k, st);
     return dispatch_ahead<T, A, C, F, false, 2>(sg, k, st, ws);
   }
   if constexpr (!HS && sizeof(T) == 4 && C == 8 && F == 2) {
@@ -747,15 +681,15 @@ int dispatch_scan_f(const Sig& sg, int k, int block, hipStream_t st, Workspace w
       // A/B (mono U2 x 512 0.811-0.820 vs 0.800-0.803) but lost 2-3.5 % in
       // bench.py's own timing, one HIP-event pair per back-to-back launch
       // (tools/tune/ab_libs.py, profiles/r02_tuning/r02_ablibs*); stereo tied
-      if (halo_bytes <= 256 && fits(2, kWG))
+      if (halo_bytes <= 256 && tile_fits<T, A, C, F, 2, kWG>(k))
         return launch_tile_scan<T, A, C, F, 2, false, kNt, kWG, false>(sg, k, st);
-      if (halo_bytes <= 4096 && fits(4, kWG))
+      if (halo_bytes <= 4096 && tile_fits<T, A, C, F, 4, kWG>(k))
         return launch_tile_scan<T, A, C, F, 4, false, kNt, kWG, false>(sg, k, st);
-      if (halo_bytes <= 8192 && fits(4, kWG))
+      if (halo_bytes <= 8192 && tile_fits<T, A, C, F, 4, kWG>(k))
         return launch_tile_scan<T, A, C, F, 4, false, kNtS, kWG, false>(sg, k, st);
-      if (halo_bytes <= 16384 && fits(4, 512))
+      if (halo_bytes <= 16384 && tile_fits<T, A, C, F, 4, 512>(k))
         return launch_tile_scan<T, A, C, F, 4, false, kNtS, 512, false>(sg, k, st);
-      if (fits(2, 1024))
+      if (tile_fits<T, A, C, F, 2, 1024>(k))
         return launch_tile_scan<T, A, C, F, 2, false, kNtS, 1024, false>(sg, k, st);
     } else {
       // fp32 mono (round 2): the halo and the tile staged by LDS-DMA, 512-thread
@@ -767,17 +701,17 @@ int dispatch_scan_f(const Sig& sg, int k, int block, hipStream_t st, Workspace w
       // vs 0.797, k=4096 0.781 vs 0.773 against the same tiles register-staged
       constexpr bool kD = true;
       constexpr int kDV = 0;
-      if (C == 1 && halo_bytes <= 8192 && fits(2, 512))
+      if (C == 1 && halo_bytes <= 8192 && tile_fits<T, A, C, F, 2, 512>(k))
         return launch_tile_scan<T, A, C, F, 2, false, kNtS, 512, true, kDV, kD>(sg, k, st);
-      if (C == 1 && halo_bytes <= 16384 && fits(4, 512))
+      if (C == 1 && halo_bytes <= 16384 && tile_fits<T, A, C, F, 4, 512>(k))
         return launch_tile_scan<T, A, C, F, 4, false, kNtS, 512, true, kDV, kD>(sg, k, st);
-      if (C == 1 && halo_bytes <= 512 && fits(2, kWG))
+      if (C == 1 && halo_bytes <= 512 && tile_fits<T, A, C, F, 2, kWG>(k))
         return launch_tile_scan<T, A, C, F, 2, false, kNt, kWG, true>(sg, k, st);
-      if (halo_bytes <= 4096 && fits(2, kWG))
+      if (halo_bytes <= 4096 && tile_fits<T, A, C, F, 2, kWG>(k))
         return launch_tile_scan<T, A, C, F, 2, false, kNtS, kWG, true>(sg, k, st);
-      if (halo_bytes <= 8192 && fits(2, 512))
+      if (halo_bytes <= 8192 && tile_fits<T, A, C, F, 2, 512>(k))
         return launch_tile_scan<T, A, C, F, 2, false, kNtS, 512, true>(sg, k, st);
-      if (halo_bytes <= 16384 && fits(4, 512))
+      if (halo_bytes <= 16384 && tile_fits<T, A, C, F, 4, 512>(k))
         return launch_tile_scan<T, A, C, F, 4, false, kNtS, 512, true>(sg, k, st);
       // fp32 halos past 16 KiB: the look-ahead scan beats the 1024-thread
       // tile (k=8192: 0.73 vs 0.69; k=12000: 0.71 vs 0.64, sweep_ahead.sh)
@@ -788,15 +722,14 @@ int dispatch_scan_f(const Sig& sg, int k, int block, hipStream_t st, Workspace w
     // long, so bigger tiles (fewer halos and barriers per byte) and the split
     // cache policy win (tools/tune/sweep_hillis.sh: fp32 k=1024 0.66 -> 0.78)
     if constexpr (sizeof(T) == 2) {
-      if (fits(4, 512))
+      if (tile_fits<T, A, C, F, 4, 512>(k))
         return launch_tile_scan<T, A, C, F, 4, HS, kNtS, 512>(sg, k, st, kRemapGroup);
     } else {
-      if (C == 1 && halo_bytes <= 512 && fits(4, kWG))
+      if (C == 1 && halo_bytes <= 512 && tile_fits<T, A, C, F, 4, kWG>(k))
         return launch_tile_scan<T, A, C, F, 4, HS, kNt>(sg, k, st, kRemapGroup);
-      if (fits(8, kWG))
+      if (tile_fits<T, A, C, F, 8, kWG>(k))
         return launch_tile_scan<T, A, C, F, 8, HS, kNtS>(sg, k, st, kRemapGroup);
     }
-    (void)kB;
     // past the LDS-staged halo: the look-ahead scan's record carry with the
     // Hillis-Steele in-tile scan (the segment kernel re-read x[n-k] from
     // global memory beyond its LDS ring: 0.25-0.40 of peak)
@@ -930,8 +863,6 @@ int dispatch_wide(const Sig& sg, int k, hipStream_t st, Workspace ws) {
       return launch_wide_ahead<T, A, C, 32, 1, kWG, kNtA, 0, 1, 8, true, true, 0, 2>(sg, k, st, ws, 384, true);
     return launch_wide_ahead<T, A, C, 4, 1, kWG, kNtA, 0, 1, 4>(sg, k, st, ws, 1024);
   }
-  (void)halo_bytes;
-  (void)ws;
   return MAVG_ERR_UNSUPPORTED;
 }
 
@@ -969,48 +900,29 @@ int dispatch_scan_c(bool vec, bool hs, const Sig& sg, int k, int block, hipStrea
 
 template <typename T, typename A>
 int dispatch_scan(int C, bool vec, bool hs, const Sig& sg, int k, int block, hipStream_t st, Workspace ws) {
-  switch (C) {
-    case 1: return dispatch_scan_c<T, A, 1>(vec, hs, sg, k, block, st, ws);
-    case 2: return dispatch_scan_c<T, A, 2>(vec, hs, sg, k, block, st, ws);
-    case 3: return dispatch_scan_c<T, A, 3>(vec, hs, sg, k, block, st, ws);
-    case 4: return dispatch_scan_c<T, A, 4>(vec, hs, sg, k, block, st, ws);
-    case 5: return dispatch_scan_c<T, A, 5>(vec, hs, sg, k, block, st, ws);
-    case 6: return dispatch_scan_c<T, A, 6>(vec, hs, sg, k, block, st, ws);
-    case 7: return dispatch_scan_c<T, A, 7>(vec, hs, sg, k, block, st, ws);
-    case 8: return dispatch_scan_c<T, A, 8>(vec, hs, sg, k, block, st, ws);
-    default: return MAVG_ERR_UNSUPPORTED;
-  }
+  return dispatch_int<1, 2, 3, 4, 5, 6, 7, 8>(C, MAVG_ERR_UNSUPPORTED, [&](auto c) {
+    return dispatch_scan_c<T, A, decltype(c)::value>(vec, hs, sg, k, block, st, ws);
+  });
 }
 
 // ---- direct LDS-tiled launch ---------------------------------------------------
 template <typename T, typename A, int C, int F, int U = 1, int WG = kWG, int NT = 0>
 int launch_direct(const Sig& sg, int k, hipStream_t st, int xcd_remap = kRemapGroup) {
   constexpr int TF = WG * F * U;
-  constexpr int VE = F * C;
-  const long long nframes = sg.nframes;
-  DirectParams p{};
-  p.in = sg.in;
-  p.out = sg.out;
-  p.hist = sg.hist;
-  p.nframes = nframes;
-  p.pre = sg.pre;
+  DirectParams p = sig_params<DirectParams>(sg, k);
   p.eio = sg.eio;
-  p.k = k;
-  p.o = make_out_params(k);
-  p.m = (k - 1 + F - 1) / F;
+  p.m = (int)direct_halo_units<F>(k);
   p.off = p.m * F - (k - 1);
   p.xcd_remap = xcd_remap;
-  const size_t lds = (((size_t)(p.m + U * WG) * VE * sizeof(T)) + 15) & ~(size_t)15;
-  if (lds > kLdsBudget) return MAVG_ERR_UNSUPPORTED;
-  const long long nblk = (nframes + TF - 1) / TF;
-  if (grid_too_large(nblk, WG)) return MAVG_ERR_UNSUPPORTED;
+  const size_t lds = DirectLds<T, C, F, U, WG>(direct_halo_units<F>(k)).bytes;
+  const long long nblk = (sg.nframes + TF - 1) / TF;
+  if (lds > kLdsBudget || grid_too_large(nblk, WG)) return MAVG_ERR_UNSUPPORTED;
   if (g_plan) {
     snprintf(g_plan->text, sizeof(g_plan->text), "direct<%s,acc=%s,C=%d,F=%d,U=%d,nt=%d> grid=%lld block=%d lds=%zu",
              type_name<T>(), type_name<A>(), C, F, U, NT, nblk, WG, lds);
     return MAVG_OK;
   }
-  hipLaunchKernelGGL((direct_kernel<T, A, C, F, U, WG, NT>), dim3((unsigned)nblk), dim3(WG), lds, st, p);
-  return hipGetLastError() == hipSuccess ? MAVG_OK : MAVG_ERR_HIP;
+  return launch_kernel<&direct_kernel<T, A, C, F, U, WG, NT>>(nblk, WG, lds, kLdsBudget, st, p);
 }
 
 // The tuned direct launch: two units per lane, non-temporal tile, halo and
@@ -1024,19 +936,13 @@ constexpr int kNtDirect = kNtLoad | kNtHalo | kNtStore;
 // the window's halo fits that workgroup's LDS").
 template <typename T, typename A, int C, int F>
 int launch_direct_block(const Sig& sg, int k, int block, hipStream_t st) {
-  auto lds_fits = [&](int U, int WG) {
-    const long long m = (k - 1 + F - 1) / F;
-    return ((m + (long long)U * WG) * F * C * (long long)sizeof(T) + 15) / 16 * 16 <= (long long)kLdsBudget;
-  };
-  const int wg = block == 0 ? 0 : block_wg(block);
-  if (wg != 0 && lds_fits(1, wg)) {
-    switch (wg) {
-      case 64: return launch_direct<T, A, C, F, 1, 64, kNtDirect>(sg, k, st);
-      case 128: return launch_direct<T, A, C, F, 1, 128, kNtDirect>(sg, k, st);
-      case 512: return launch_direct<T, A, C, F, 1, 512, kNtDirect>(sg, k, st);
-      case 1024: return launch_direct<T, A, C, F, 1, 1024, kNtDirect>(sg, k, st);
-      default: return launch_direct<T, A, C, F, 1, kWG, kNtDirect>(sg, k, st);
-    }
+  if (block != 0) {
+    const int s = dispatch_int<64, 128, 256, 512, 1024>(block_wg(block), kNoFit, [&](auto wg) {
+      constexpr int WG = decltype(wg)::value;
+      if (DirectLds<T, C, F, 1, WG>(direct_halo_units<F>(k)).bytes > kLdsBudget) return kNoFit;
+      return launch_direct<T, A, C, F, 1, WG, kNtDirect>(sg, k, st);
+    });
+    if (s != kNoFit) return s;
   }
   return launch_direct<T, A, C, F, 2, kWG, kNtDirect>(sg, k, st);
 }
@@ -1059,17 +965,9 @@ int dispatch_direct_c(int width, const Sig& sg, int k, int block, hipStream_t st
 
 template <typename T, typename A>
 int dispatch_direct(int C, int width, const Sig& sg, int k, int block, hipStream_t st) {
-  switch (C) {
-    case 1: return dispatch_direct_c<T, A, 1>(width, sg, k, block, st);
-    case 2: return dispatch_direct_c<T, A, 2>(width, sg, k, block, st);
-    case 3: return dispatch_direct_c<T, A, 3>(width, sg, k, block, st);
-    case 4: return dispatch_direct_c<T, A, 4>(width, sg, k, block, st);
-    case 5: return dispatch_direct_c<T, A, 5>(width, sg, k, block, st);
-    case 6: return dispatch_direct_c<T, A, 6>(width, sg, k, block, st);
-    case 7: return dispatch_direct_c<T, A, 7>(width, sg, k, block, st);
-    case 8: return dispatch_direct_c<T, A, 8>(width, sg, k, block, st);
-    default: return MAVG_ERR_UNSUPPORTED;
-  }
+  return dispatch_int<1, 2, 3, 4, 5, 6, 7, 8>(C, MAVG_ERR_UNSUPPORTED, [&](auto c) {
+    return dispatch_direct_c<T, A, decltype(c)::value>(width, sg, k, block, st);
+  });
 }
 
 // naive: one thread per sample, exactly `block` threads per workgroup (any

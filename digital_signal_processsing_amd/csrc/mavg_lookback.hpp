@@ -400,6 +400,23 @@ __device__ __forceinline__ void run_total(const T* __restrict__ in, const gran_t
 #define MAVG_ANOW() 0ull
 #endif
 
+// The dynamic LDS of one workgroup, as byte offsets: the shifted-tile stage (the tile's units and
+// one more for a misaligned x[n-k]), [NW][C] carry partials, [NSEG][C] segment totals, [3][NW][C]
+// wave shares of the records published here and (HS) the tile itself, [U*WG] units, 16-B aligned.
+// The kernel, its layout check and launch_ahead_scan all read it from here.
+template <typename T, typename A, int C, int F, int U, int WG, bool HS>
+struct AheadLds {
+  using SA = typename ScanAcc<T, A>::type;
+  static constexpr int NW = WG / 64;
+  static constexpr int NSEG = U * NW;
+  static constexpr int stage_units = U * WG + 1;
+  static constexpr size_t hsum = (((size_t)stage_units * F * C * sizeof(T)) + 15) & ~(size_t)15;
+  static constexpr size_t tot = hsum + (size_t)NW * C * sizeof(A);
+  static constexpr size_t shares = tot + (size_t)NSEG * C * sizeof(SA);
+  static constexpr size_t tstage = (shares + (size_t)3 * NW * C * sizeof(SA) + 15) & ~(size_t)15;
+  static constexpr size_t bytes = HS ? tstage + (size_t)U * WG * F * C * sizeof(T) : shares + (size_t)3 * NW * C * sizeof(SA);
+};
+
 template <typename T, typename A, int C, int F, int U, int NT, bool RC = false, bool DMA = true, bool WREC = false,
           int DV = 0, bool HS = false, bool RUNS = false, int WG_ = kWG>
 __global__ __launch_bounds__(WG_) void ahead_scan_kernel(AheadParams p) {
@@ -410,8 +427,8 @@ __global__ __launch_bounds__(WG_) void ahead_scan_kernel(AheadParams p) {
   constexpr int VE = F * C;
   constexpr int TF = WG * F * U;
   constexpr int NSEG = U * NW;
-  constexpr int kStageUnits = U * WG + 1;
-  constexpr int kStageBytes = ((kStageUnits * VE * (int)sizeof(T)) + 15) & ~15;
+  using Lds = AheadLds<T, A, C, F, U, WG, HS>;
+  constexpr int kStageUnits = Lds::stage_units;
   using IO = UnitIO<T, VE>;
   using U_t = Unit<T, VE>;
   using SA = typename ScanAcc<T, A>::type;
@@ -422,12 +439,10 @@ __global__ __launch_bounds__(WG_) void ahead_scan_kernel(AheadParams p) {
 
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   T* stage = reinterpret_cast<T*>(smem);
-  A* hsum = reinterpret_cast<A*>(smem + kStageBytes);  // [NW][C] carry partials
-  SA* tot = reinterpret_cast<SA*>(hsum + NW * C);       // [NSEG][C] segment totals
-  SA* shares = tot + NSEG * C;                           // [3][NW][C] wave shares of the records published here
-  // HS: the tile itself, [U*WG] units, after the shares (16-B aligned)
-  T* tstage = reinterpret_cast<T*>(smem + ((kStageBytes + (NW * C * (int)sizeof(A)) +
-                                            (NSEG + 3 * NW) * C * (int)sizeof(SA) + 15) & ~15));
+  A* hsum = reinterpret_cast<A*>(smem + Lds::hsum);       // [NW][C] carry partials
+  SA* tot = reinterpret_cast<SA*>(smem + Lds::tot);        // [NSEG][C] segment totals
+  SA* shares = reinterpret_cast<SA*>(smem + Lds::shares);  // [3][NW][C] wave shares of the records published here
+  T* tstage = reinterpret_cast<T*>(smem + Lds::tstage);    // HS: the tile itself, [U*WG] units, after the shares
 
   const T* __restrict__ in = static_cast<const T*>(p.in);
   T* __restrict__ out = static_cast<T*>(p.out);
@@ -448,6 +463,7 @@ __global__ __launch_bounds__(WG_) void ahead_scan_kernel(AheadParams p) {
   const int Ha = p.halo_units * F;
   const long long h0 = t0 - Ha;
   MAVG_DCHECK(tile >= 0 && tile < (long long)gridDim.x && t0 < nframes, "ahead tile index", tile, gridDim.x);
+  MAVG_DCHECK(Lds::bytes <= kLdsBudget, "ahead LDS layout", Lds::bytes, kStageUnits);
   const bool tile_full = (t0 + TF <= nframes);
   if (tid == 0) MAVG_ATRACE(0, MAVG_ANOW());
   const long long a = t0 - k;                                   // first frame of the window before t0

@@ -36,6 +36,21 @@ struct TileParams {
   OutParams o;
 };
 
+// The dynamic LDS of one workgroup, as byte offsets: the stage (halo, tile, one pad unit), [NSEG][C]
+// segment totals, [NW][C] halo partial sums.  launch_tile_scan and tile_fits read it from here.  The
+// kernel carves its pointers with one int expression of its own (a call on the run-time halo_units,
+// however inlined, changed the code of the LDS-DMA tiles); its debug build checks them against this.
+template <typename T, typename A, int C, int F, int U, int WG>
+struct TileLds {
+  static constexpr int NW = WG / 64;
+  static constexpr int NSEG = U * NW;
+  size_t tot, hsum, bytes;
+  __host__ __device__ constexpr explicit TileLds(size_t halo_units)
+      : tot((((halo_units + (size_t)U * WG + 1) * F * C * sizeof(T)) + 15) & ~(size_t)15),
+        hsum(tot + (size_t)NSEG * C * sizeof(A)),
+        bytes(hsum + (size_t)NW * C * sizeof(A)) {}
+};
+
 // HS: Hillis-Steele flavour.  Transposed ownership: lane l holds frames l,
 //     l+64, ..., l+64(F-1) of its 64F-frame wave segment, so every register
 //     holds 64 consecutive frames and the log-step scan runs on DPP (6 steps
@@ -68,6 +83,8 @@ __global__ __launch_bounds__(WG) void tile_scan_kernel(TileParams p) {
   T* stage = reinterpret_cast<T*>(smem);     // [Hu + U*256 + 1 pad] units
   A* tot = reinterpret_cast<A*>(smem + stage_bytes);  // [NSEG][C] segment totals
   A* hsum = tot + NSEG * C;                            // [NW][C] halo partial sums
+  MAVG_DCHECK(lds_layout_ok(TileLds<T, A, C, F, U, WG>((size_t)Hu), smem, tot, hsum, lds_budget(WG)),
+              "tile LDS layout", stage_bytes, Hu);
 
   const T* __restrict__ in = static_cast<const T*>(p.in);
   T* __restrict__ out = static_cast<T*>(p.out);
@@ -86,8 +103,6 @@ __global__ __launch_bounds__(WG) void tile_scan_kernel(TileParams p) {
   const long long t0 = tile * TF;
   const long long h0 = t0 - Ha;              // first staged halo frame
   MAVG_DCHECK(tile >= 0 && tile < p.ntiles && t0 < nframes, "tile index", tile, p.ntiles);
-  MAVG_DCHECK(stage_bytes + (NSEG + NW) * C * (int)sizeof(A) <= (int)(WG >= 1024 ? 80 * 1024 : 64 * 1024),
-              "tile LDS layout", stage_bytes, Hu);
   const bool tile_full = (t0 + TF <= nframes);
 
   constexpr bool kDma = DMA && !HS && IO::kVec && VE * (int)sizeof(T) == 16;

@@ -61,6 +61,23 @@ struct WideParams {
   int pre;        // frames in front of `in` that are readable signal (load_elem)
   OutParams o;
 };
+// WideParams::halo_g of a k-frame window: the granules covering it, in whole 256-B LDS rows
+template <typename T, int C>
+constexpr long long wide_halo_granules(int k) { return (((long long)k * C * (int)sizeof(T) + 15) / 16 + 15) / 16 * 16; }
+
+// The dynamic LDS of one wide-tile workgroup, as byte offsets: the swizzled stage of halo_g + TG
+// granules, [NSEG][C] segment totals, [NW][C] halo partial sums.  launch_wide_tile reads it from
+// here; the kernel's debug build checks the pointers it carves against it (as TileLds).
+template <typename T, typename A, int C, int P, int U, int WG>
+struct WideTileLds {
+  static constexpr int NW = WG / 64;
+  static constexpr int NSEG = U * NW;
+  static constexpr int TF = WG * P * U;                           // tile frames
+  static constexpr int TG = TF * C * (int)sizeof(T) / 16;         // tile granules
+  size_t tot, hsum, bytes;
+  __host__ __device__ constexpr explicit WideTileLds(size_t halo_g)
+      : tot((halo_g + TG) * 16), hsum(tot + (size_t)NSEG * C * sizeof(A)), bytes(hsum + (size_t)NW * C * sizeof(A)) {}
+};
 
 // stage: logical granule -> LDS slot (QM = 3 for 64-B chunks, 7 for 128-B chunks)
 template <int QM>
@@ -113,8 +130,9 @@ __global__ __launch_bounds__(WG) void wide_tile_kernel(WideParams p) {
   constexpr int G = CE / EPG;               // granules per lane chunk
   static_assert(CE % EPG == 0 && (G == 4 || G == 8), "64-B or 128-B chunks");
   constexpr int QM = G == 4 ? 3 : 7;
-  constexpr int TF = WG * P * U;  // tile frames
-  constexpr int TG = WG * U * G;  // tile granules
+  using Lds = WideTileLds<T, A, C, P, U, WG>;
+  constexpr int TF = Lds::TF;  // tile frames
+  constexpr int TG = Lds::TG;  // tile granules (WG * U * G)
   constexpr int NSEG = U * NW;
   using IO = UnitIO<T, EPG>;
   using Gr = Unit<T, EPG>;
@@ -142,6 +160,7 @@ __global__ __launch_bounds__(WG) void wide_tile_kernel(WideParams p) {
   const long long h0 = t0 - Hf;
   MAVG_DCHECK(tile >= 0 && tile < p.ntiles && t0 < nframes, "wide tile index", tile, p.ntiles);
   MAVG_DCHECK(Hf >= k && Hg % 16 == 0, "wide halo", Hf, k);
+  MAVG_DCHECK(lds_layout_ok(Lds((size_t)Hg), smem, tot, hsum, kWideLdsBudget), "wide tile LDS layout", Hg, TG);
   const bool tile_full = t0 + TF <= nframes;
   const bool dma = tile_full && h0 >= 0;  // uniform
 
@@ -446,6 +465,20 @@ __device__ __forceinline__ void xl_transpose(uint32_t (&xr)[P], int cl) {
   }
 }
 
+// The dynamic LDS of one chan-tile workgroup, as byte offsets: the swizzled stage of halo_g granules
+// and, unless XG (the halo-only form), the tile's TG; [NW][C] wave-segment totals; [NW][C] halo partial
+// sums.  launch_chan_tile reads it; the kernel's debug build checks its pointers against it (as TileLds).
+template <typename T, typename A, int C, int Q, int WG, bool XG>
+struct ChanTileLds {
+  static constexpr int NW = WG / 64;
+  static constexpr int CL = C * (int)sizeof(T) / 4;        // dword columns per frame (a lane's)
+  static constexpr int TF = NW * (64 / CL) * Q;            // waves x frame blocks x frames per block
+  static constexpr int TG = TF * C * (int)sizeof(T) / 16;  // tile granules
+  size_t tot, hsum, bytes;
+  __host__ __device__ constexpr explicit ChanTileLds(size_t halo_g)
+      : tot((halo_g + (XG ? 0 : TG)) * 16), hsum(tot + (size_t)NW * C * sizeof(A)), bytes(hsum + (size_t)NW * C * sizeof(A)) {}
+};
+
 // IP (XG only, the launcher's choice when the staged halo is exactly k frames): each output is
 // written in pass 2 over the x[n-k] it last read -- the same lane and address, as in the wide
 // look-ahead -- so no barrier before the output stage and no Q output registers
@@ -463,9 +496,10 @@ __global__ __launch_bounds__(WG) void chan_tile_kernel(WideParams p) {
   constexpr int GPF = CL / 4;   // 16-B granules per frame
   constexpr int EPG = 16 / (int)sizeof(T);  // samples per granule
   static_assert(ilog2c(GPF) + ilog2c(NB) == 4 && Q * GPF >= 16, "the key spans one bank row, outside its bits");
+  using Lds = ChanTileLds<T, A, C, Q, WG, XG>;
   constexpr int WF = NB * Q;    // frames per wave
-  constexpr int TF = NW * WF;   // tile frames
-  constexpr int TG = TF * GPF;  // tile granules
+  constexpr int TF = Lds::TF;   // tile frames (NW * WF)
+  constexpr int TG = Lds::TG;   // tile granules (TF * GPF)
   using IO = UnitIO<T, EPG>;
   using Gr = Unit<T, EPG>;
 
@@ -494,6 +528,7 @@ __global__ __launch_bounds__(WG) void chan_tile_kernel(WideParams p) {
   const long long h0 = t0 - Hf;
   MAVG_DCHECK(tile >= 0 && tile < p.ntiles && t0 < nframes, "chan tile index", tile, p.ntiles);
   MAVG_DCHECK(Hf >= k && Hg % 16 == 0, "chan halo", Hf, k);
+  MAVG_DCHECK(lds_layout_ok(Lds((size_t)Hg), smem, tot, hsum, kWideLdsBudget), "chan tile LDS layout", Hg, TG);
   MAVG_DCHECK(!XG || (k >= TF && Hg >= TG), "chan XG window", k, TF);
   const bool tile_full = t0 + TF <= nframes;
   constexpr int kTileStaged = XG ? 0 : TG;  // granules of the tile in the stage
@@ -757,6 +792,25 @@ namespace mavg {
 // 92 at C = 4) reaches the LDS-sized 4 workgroups per CU without it.
 // XL (round 6, XG): x as 16-B frame-piece loads plus quad transposes (xl_load), transposed after
 // the first barrier so the loads stay in flight behind the stage and phase A.
+// The dynamic LDS of one wide look-ahead workgroup, as byte offsets: the shifted tile (SG = TG + 1
+// swizzled granules), unless XG the tile (TG), then ahead_scan_kernel's [NW][C] carry partials,
+// [NSEG][C] segment totals, [3][NW][C] record shares.  Read by the kernel, its layout check and launch_wide_ahead.
+template <typename T, typename A, int C, int P, int UW, int WG, bool CH, bool XG>
+struct WideAheadLds {
+  using SA = typename ScanAcc<T, A>::type;
+  static constexpr int NW = WG / 64;
+  static constexpr int NSEG = UW * NW;
+  static constexpr int CL = C * (int)sizeof(T) / 4 > 0 ? C * (int)sizeof(T) / 4 : 1;  // CH: dword columns per frame
+  static constexpr int TF = CH ? NW * (64 / CL) * P : WG * P * UW;  // CH: P frames of one dword column per lane
+  static constexpr int TG = TF * C * (int)sizeof(T) / 16;           // tile granules
+  static constexpr int SG = TG + 1;                                  // shifted-tile granules
+  static constexpr size_t tstage = (size_t)SG * 16;
+  static constexpr size_t hsum = tstage + (size_t)(XG ? 0 : TG) * 16;
+  static constexpr size_t tot = hsum + (size_t)NW * C * sizeof(A);
+  static constexpr size_t shares = tot + (size_t)NSEG * C * sizeof(SA);
+  static constexpr size_t bytes = shares + (size_t)3 * NW * C * sizeof(SA);
+};
+
 template <typename T, typename A, int C, int P, int UW, int WG, int NT, int DV, int F, int U, bool CH = false,
           bool XG = false, int MW = 0, int XL = 0>
 __global__ __launch_bounds__(WG, MW > 0 ? MW : 1) void wide_ahead_kernel(AheadParams p) {
@@ -777,10 +831,11 @@ __global__ __launch_bounds__(WG, MW > 0 ? MW : 1) void wide_ahead_kernel(AheadPa
   constexpr int QM = G == 4 ? 3 : 7;
   constexpr int NB = 64 / CL;              // CH: frame blocks per wave
   constexpr int WF = NB * P;               // CH: frames per wave
-  constexpr int TF = CH ? NW * WF : WG * P * UW;
+  using Lds = WideAheadLds<T, A, C, P, UW, WG, CH, XG>;
+  constexpr int TF = Lds::TF;      // CH ? NW * WF : WG * P * UW
   static_assert(TF == WG * F * U, "the record units tile the same frames as the chunks");
-  constexpr int TG = TF * C / EPG;  // tile granules
-  constexpr int SG = TG + 1;       // shifted-tile granules (one more for an x[n-k] extraction)
+  constexpr int TG = Lds::TG;      // tile granules
+  constexpr int SG = Lds::SG;      // shifted-tile granules (one more for an x[n-k] extraction)
   constexpr int NSEG = UW * NW;
   constexpr int VE = F * C;
   using IO = UnitIO<T, VE>;
@@ -791,10 +846,10 @@ __global__ __launch_bounds__(WG, MW > 0 ? MW : 1) void wide_ahead_kernel(AheadPa
 
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   unsigned char* sstage = smem;              // [SG] shifted tile, swizzled granules (XG: then the outputs)
-  unsigned char* tstage = smem + SG * 16;    // [TG] the tile, swizzled granules (then the outputs); XG: absent
-  A* hsum = reinterpret_cast<A*>(tstage + (XG ? 0 : TG) * 16);  // [NW][C]
-  SA* tot = reinterpret_cast<SA*>(hsum + NW * C);    // [NSEG][C]
-  SA* shares = tot + NSEG * C;                         // [3][NW][C]
+  unsigned char* tstage = smem + Lds::tstage;  // [TG] the tile, swizzled granules (then the outputs); XG: absent
+  A* hsum = reinterpret_cast<A*>(smem + Lds::hsum);        // [NW][C]
+  SA* tot = reinterpret_cast<SA*>(smem + Lds::tot);        // [NSEG][C]
+  SA* shares = reinterpret_cast<SA*>(smem + Lds::shares);  // [3][NW][C]
 
   const T* __restrict__ in = static_cast<const T*>(p.in);
   T* __restrict__ out = static_cast<T*>(p.out);
@@ -814,6 +869,7 @@ __global__ __launch_bounds__(WG, MW > 0 ? MW : 1) void wide_ahead_kernel(AheadPa
   const int Ha = p.halo_units * F;  // the shifted stage starts Ha >= k frames before the tile
   const long long h0 = t0 - Ha;
   MAVG_DCHECK(tile >= 0 && tile < (long long)gridDim.x && t0 < nframes, "wide ahead tile index", tile, gridDim.x);
+  MAVG_DCHECK(Lds::bytes <= kWideLdsBudget, "wide ahead LDS layout", Lds::bytes, SG);
   const bool tile_full = t0 + TF <= nframes;
   const long long a = t0 - k;
   const long long jlo = a >= 0 ? (a + TF - 1) / TF : 0;

@@ -402,3 +402,57 @@ def test_direct_block_size_falls_back_when_the_halo_does_not_fit():
     p = dsp.plan(1 << 20, 13_000, algo="direct", block_size=1024)
     assert p == dsp.plan(1 << 20, 13_000, algo="direct") and "U=2" in p and "block=256" in p, p
     assert "block=1024" in dsp.plan(1 << 20, 1000, algo="direct", block_size=1024)
+
+
+# (n, k, channels, dtype, algo, block_size) -> the kernel, its lds= and its ws= (None: no workspace),
+# recorded from the library before the layouts moved into the kernels' *Lds structs and AheadLaunch
+# (csrc/mavg_launch.hpp): literals, never recomputed from those helpers.  One case per launcher
+# family, each where every term of that layout is non-zero.
+_PINNED_LAYOUTS = [
+    # tile scan with a halo; 6-B units: the stage's round-up to 16 B counts
+    ((1 << 30, 1024, 1, _lib.F32, "auto", 0), "tile_scan<f32,acc=f64,C=1,F=4,U=2,", 20688, None),
+    ((3 << 20, 100, 3, _lib.I16, "blelloch", 0), "tile_scan<i16,acc=i32,C=3,F=1,U=4,", 6992, None),
+    # look-ahead: Hillis-Steele (the extra tile stage), per-wave records, run totals (run_bytes),
+    # self-published 32-KiB tiles
+    ((1 << 30, 70_000, 1, _lib.F32, "hillis", 0), "ahead_scan<f32,acc=f64,C=1,F=4,U=4,hillis,", 33040, 16777232),
+    ((1 << 30, 20_000, 1, _lib.F32, "auto", 0), "ahead_scan<f32,acc=f64,C=1,F=4,U=4,blelloch,", 16656, 16777232),
+    ((1 << 30, 10_000_000, 1, _lib.F32, "auto", 0), "ahead_scan<f32,acc=f64,C=1,F=4,U=4,blelloch,", 16656, 4317456),
+    ((1 << 30, 20_000, 2, _lib.I16, "auto", 0), "ahead_scan<i16,acc=i32,C=2,F=4,U=8,blelloch,", 33168, 1048592),
+    # wide tile; chan tile without and with xg (and in place)
+    ((1 << 30, 1024, 2, _lib.F32, "auto", 0), "wide_tile<f32,acc=f64,C=2,P=16,U=1,", 41088, None),
+    ((1 << 30, 100, 8, _lib.F32, "auto", 0), "chan_tile<f32,acc=f64,C=8,Q=32,nt=13,dv=0>", 36608, None),
+    ((1 << 30, 1024, 8, _lib.F32, "auto", 0), "chan_tile<f32,acc=f64,C=8,Q=32,nt=13,dv=0,xg=1>", 33280, None),
+    ((1 << 30, 2048, 4, _lib.F32, "auto", 0), "chan_tile<f32,acc=f64,C=4,Q=32,nt=13,dv=0,xg=1,ip=1,xl=1>", 33024, None),
+    # wide look-ahead with xg, and without (chunks; int64 sums)
+    ((1 << 30, 44_100, 8, _lib.F32, "auto", 0), "wide_ahead<f32,acc=f64,C=8,P=32,U=1,nt=9,dv=0,F=1,FU=4,ch=1,xg=1,", 34064,
+     16777232),
+    ((1 << 30, 600_000, 2, _lib.F32, "auto", 0), "wide_ahead<f32,acc=f64,C=2,P=8,U=1,nt=9,dv=0,F=2,FU=4,mw=0,", 33104, 8388624),
+    ((1 << 30, 70_000, 8, _lib.I16, "auto", 0), "wide_ahead<i16,acc=i64,C=8,P=4,U=1,nt=9,dv=0,F=1,FU=4,mw=0,", 33552, 8388624),
+    # direct with block set; 6-B units: the round-up counts
+    ((1 << 30, 100, 1, _lib.F32, "direct", 512), "direct<f32,acc=f64,C=1,F=4,U=1,", 8592, None),
+    ((3 << 20, 77, 3, _lib.I16, "direct_scalar", 128), "direct<i16,acc=i32,C=3,F=1,U=1,", 1232, None),
+]
+
+
+@pytest.mark.parametrize("args,kernel,lds,ws", _PINNED_LAYOUTS)
+def test_pinned_lds_and_workspace_layouts(args, kernel, lds, ws):
+    import digital_signal_processsing_amd as dsp
+    p = dsp.plan(*args)
+    assert p.startswith(kernel), p
+    assert re.search(r" lds=(\d+)", p).group(1) == str(lds), p
+    if ws is None:
+        assert " ws=" not in p, p
+    else:
+        assert p.endswith(f" ws={ws}"), p
+
+
+def test_block_size_falls_back_when_only_the_round_up_overflows():
+    """int16 mono in frame units (2-B units), 64 threads: at k = 32633 the stage is 65524 B before
+    its round-up to 16 B; with the 12 B of totals the tile is 65536 B unrounded and 65548 B as
+    launched.  The dispatch rule asks the launcher's own layout, so the window takes the tuned
+    dispatch (mavg.h: "while the window's halo fits that workgroup's LDS") instead of
+    MAVG_ERR_UNSUPPORTED."""
+    import digital_signal_processsing_amd as dsp
+    p = dsp.plan(1 << 20, 32_633, algo="blelloch_scalar", dtype=_lib.I16, block_size=64)
+    assert p == dsp.plan(1 << 20, 32_633, algo="blelloch_scalar", dtype=_lib.I16) and "block=1024" in p, p
+    assert "block=64" in dsp.plan(1 << 20, 32_625, algo="blelloch_scalar", dtype=_lib.I16, block_size=64)

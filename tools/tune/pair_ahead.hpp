@@ -486,60 +486,28 @@ int launch_pair_ahead(const Sig& sg, int k, hipStream_t st, Workspace ws, int ah
   static_assert(TF == WG * U, "F = 1 record units");
   constexpr int TG = TF * C / EPG;
   using SA = typename ScanAcc<T, A>::type;
-  const long long nframes = sg.nframes;
   if (ahead_past_l2(k, C, sizeof(T), TF) || (long long)k < TF) return MAVG_ERR_UNSUPPORTED;
-  ahead &= ~7;
-  int spin = kAheadSpin;
-#ifdef MAVG_TEST_HOOKS
-  {
-    const int t = g_test_ahead_slots.load(std::memory_order_relaxed);
-    if (t >= 0) ahead = t & ~7;
-  }
-  {
-    const int t = g_test_ahead_spin.load(std::memory_order_relaxed);
-    if (t >= 0) spin = t;
-  }
-#endif
-  const long long ntiles = (nframes + TF - 1) / TF;
-  const long long nfull = nframes / TF;
-  if (ntiles > 0x7fffffffLL) return MAVG_ERR_UNSUPPORTED;
-  const long long q8 = (ntiles + 7) / 8;               // run positions of the longest run
+  AheadLaunch g;  // short of the L2 reach: remap mode 1; per-tile records, no run totals
+  const int gs = g.make<T, A, C>(sg, k, ahead, TF, WG, 1, false);
+  if (gs != MAVG_OK) return gs;
+  const long long q8 = (g.ntiles + 7) / 8;             // run positions of the longest run
   const long long grid = 8 * ((q8 + 1) / 2);           // a workgroup per pair of positions per XCD
-  const size_t need = ahead_granule_bytes<T, A, C, 1, U>(nfull);
   const size_t lds = (size_t)2 * (TG + 1) * 16 + (size_t)(NW * C + C) * sizeof(A) + (size_t)(2 + 6) * NW * C * sizeof(SA);
   if (lds > 64 * 1024) return MAVG_ERR_UNSUPPORTED;
   if (g_plan) {
     snprintf(g_plan->text, sizeof(g_plan->text),
              "pair_ahead<%s,acc=%s,C=%d,P=%d,nt=%d,dv=%d,FU=%d,xl=%d> grid=%lld block=%d lds=%zu tile_frames=%d "
              "ahead=%d remap=1 tiles=%lld ws=%zu",
-             type_name<T>(), type_name<A>(), C, P, NT, DV, U, XL, grid, WG, lds, TF, ahead, ntiles, need);
-    g_plan->ws_bytes = need;
+             type_name<T>(), type_name<A>(), C, P, NT, DV, U, XL, grid, WG, lds, TF, g.ahead, g.ntiles, g.need);
+    g_plan->ws_bytes = g.need;
     return MAVG_OK;
   }
-  if (ws.ptr == nullptr || ws.bytes < need) return MAVG_ERR_WORKSPACE;
-  if ((reinterpret_cast<uintptr_t>(ws.ptr) & 15u) != 0) return MAVG_ERR_MISALIGNED;
-  if (hipMemsetAsync(ws.ptr, 0, need, st) != hipSuccess) return MAVG_ERR_HIP;
-  AheadParams p{};
-  p.in = sg.in;
-  p.out = sg.out;
-  p.hist = sg.hist;
-  p.nframes = nframes;
-  p.pre = sg.pre;
+  AheadParams p;
+  const int s = g.begin(p, sg, k, false, ws, st);
+  if (s != MAVG_OK) return s;
   p.eio = 0;
-  p.nfull = nfull;
-  p.k = k;
-  p.o = make_out_params(k);
   p.halo_units = k;
   p.xk_off = 0;
-  p.xcd_remap = 1;
-  p.runs_done = 0;
-  p.ahead = ahead;
-  p.head = (int)std::min<long long>((long long)k / TF, nfull);
-  p.spin = spin;
-  p.self = 0;
-  p.gran = static_cast<unsigned long long*>(ws.ptr);
-  p.runs = nullptr;
-  p.stats = static_cast<unsigned char*>(ws.ptr) + need - 16;
   hipLaunchKernelGGL((pair_ahead_kernel<T, A, C, P, WG, NT, DV, U, XL>), dim3((unsigned)grid), dim3(WG), lds, st, p);
   return hipGetLastError() == hipSuccess ? MAVG_OK : MAVG_ERR_HIP;
 }
