@@ -9,6 +9,7 @@ only for device memory and streams.
     y = moving_average(x, grade=32, channels=2, algo="hillis")
     y = moving_average_rows(x, grade=1024)             # [B, T] / [C, T] / [B, C, T]: every row on its own
     y = moving_average_ragged(x, grade=1024, lengths=[5, 0, 30011, 7])   # packed rows of different lengths
+    y = moving_average_decimated(x, grade=400, hop=160)  # only every hop-th output frame, in one launch
 
 Semantics: ``basics/profilable_moving_averager.cpp:14-37`` -- interleaved
 frames, window ``grade`` frames, zero history (or ``history``: the
@@ -34,6 +35,11 @@ __all__ = [
     "moving_average_ragged_into",
     "ragged_plan",
     "ragged_workspace_bytes",
+    "moving_average_decimated",
+    "moving_average_decimated_into",
+    "decim_out_frames",
+    "decim_plan",
+    "decim_workspace_bytes",
     "fill_synthetic",
     "workspace_bytes",
     "resolve_algo",
@@ -139,18 +145,22 @@ def _loop_workspace(ws_n: int, workspace, stream, device, query: str):
     return _on_stream(stream, lambda: torch.empty(ws_n, dtype=torch.uint8, device=device)), ws_n
 
 
-def _with_out(x, stream, into, inputs):
-    """``out = empty_like(x)`` filled by ``into(out)``.  On a launch stream other than the
+def _with_out(x, stream, into, inputs, shape=None):
+    """``out = empty_like(x)`` (with ``shape``: that shape, ``x``'s dtype and device) filled by
+    ``into(out)``.  On a launch stream other than the
     current one, the launch stream waits for the current one (where ``inputs`` come from),
     ``out`` is allocated on the launch stream, and the caching allocator is kept from handing
     the inputs' blocks out again before the kernel that reads them there ends."""
     torch = _torch()
+    def make():
+        return torch.empty_like(x) if shape is None else torch.empty(shape, dtype=x.dtype, device=x.device)
+
     if stream is None or stream == torch.cuda.current_stream(x.device):
-        out = torch.empty_like(x)
+        out = make()
         into(out)
         return out
     stream.wait_stream(torch.cuda.current_stream(x.device))
-    out = _on_stream(stream, lambda: torch.empty_like(x))
+    out = _on_stream(stream, make)
     into(out)
     for t in inputs:
         if t is not None:
@@ -441,6 +451,104 @@ def moving_average_ragged(x, grade: int, offsets=None, lengths=None, channels: i
     _check_device_x(x)
     return _with_out(x, stream, lambda out: moving_average_ragged_into(x, out, grade, offsets, lengths, channels,
                                                                        offsets_device, stream, library=library), (x,))
+
+
+def _check_hop_phase(hop: int, phase: int) -> None:
+    if hop < 1:
+        raise ValueError(f"hop must be >= 1, got {hop}")
+    if not 0 <= phase < hop:
+        raise ValueError(f"phase must be in [0, hop) = [0, {hop}), got {phase}")
+
+
+def decim_out_frames(n_frames: int, hop: int, phase: int = 0, library: Optional[str] = None) -> int:
+    """``len(range(phase, n_frames, hop))``: the frames ``moving_average_decimated`` returns."""
+    import ctypes
+    _check_hop_phase(hop, phase)
+    out = ctypes.c_size_t(0)
+    _lib.check(_lib.load(library).mavg_decim_out_frames(n_frames, hop, phase, ctypes.byref(out)), "mavg_decim_out_frames")
+    return out.value
+
+
+def decim_workspace_bytes(n: int, grade: int, hop: int, phase: int = 0, channels: int = 1, dtype: int = F32,
+                          library: Optional[str] = None) -> int:
+    """Device workspace ``moving_average_decimated_into`` needs: 0 for the one-launch paths
+    (``decim_scan``, ``decim_window``), the full-rate output plus ``workspace_bytes`` for
+    ``decim_full``, ``workspace_bytes`` for ``hop == 1``."""
+    import ctypes
+    _check_hop_phase(hop, phase)
+    out = ctypes.c_size_t(0)
+    _lib.check(_lib.load(library).mavg_decim_workspace_bytes(n, channels, grade, hop, phase, dtype, ctypes.byref(out)),
+               "mavg_decim_workspace_bytes")
+    return out.value
+
+
+def decim_plan(n: int, grade: int, hop: int, phase: int = 0, channels: int = 1, dtype: int = F32,
+               library: Optional[str] = None) -> str:
+    """What mavg_decim_run would do (nothing is launched): ``decim_none x <plan>``,
+    ``decim_window<...> ...``, ``decim_scan<...> ... tile_frames=N ...`` or
+    ``decim_full hop=H phase=P x <plan>``."""
+    import ctypes
+    _check_hop_phase(hop, phase)
+    buf = ctypes.create_string_buffer(512)
+    _lib.check(_lib.load(library).mavg_decim_plan(n, channels, grade, hop, phase, dtype, buf, len(buf)), "mavg_decim_plan")
+    return buf.value.decode()
+
+
+def _decim_shape(x, channels: int):
+    """(frames, channels) of a signal for the decimated calls: ``[n]`` interleaved samples with
+    ``channels`` channels, or ``[frames, C]``."""
+    if channels < 1:
+        raise ValueError(f"channels must be >= 1, got {channels}")
+    if x.dim() == 1:
+        if x.shape[0] % channels:
+            raise ValueError(f"x holds {x.shape[0]} samples, not a multiple of channels={channels}")
+        return x.shape[0] // channels, channels
+    if x.dim() == 2:
+        if channels not in (1, x.shape[1]):
+            raise ValueError(f"with channels={channels} a 2-D x must be [frames, {channels}], got {tuple(x.shape)}")
+        return x.shape[0], x.shape[1]
+    raise ValueError(f"x must be [samples] or [frames, channels], got {tuple(x.shape)}")
+
+
+def moving_average_decimated_into(x, out, grade: int, hop: int, phase: int = 0, channels: int = 1, history=None,
+                                  stream=None, workspace=None, library: Optional[str] = None) -> None:
+    """Enqueue ``out = moving_average_decimated(x)`` on ``stream`` (default: current).
+
+    ``out``: a contiguous device tensor of ``decim_out_frames(frames, hop, phase) * channels``
+    samples.  ``workspace``: as in ``moving_average_rows_into``; only the full-rate fallback (and
+    ``hop == 1`` at long windows) needs one (``decim_workspace_bytes``)."""
+    _check_hop_phase(hop, phase)
+    frames, C = _decim_shape(x, channels)
+    if x.dtype != out.dtype:
+        raise ValueError("x and out must have the same dtype")
+    M = len(range(phase, frames, hop))
+    if out.numel() != M * C:
+        raise ValueError(f"out must hold out_frames * channels = {M} * {C} samples, got {out.numel()}")
+    _check_device_pair(x, out)
+    dt = _dtype_code(x)
+    hist_ptr = _history_ptr(history, x, (grade - 1) * C, "(grade-1)*channels")
+    ws_n = decim_workspace_bytes(x.numel(), grade, hop, phase, C, dt, library)
+    ws, ws_n = _loop_workspace(ws_n, workspace, stream, x.device, "decim_workspace_bytes")
+    st = _lib.load(library).mavg_decim_run(x.data_ptr(), out.data_ptr(), x.numel(), C, grade, hop, phase, dt, hist_ptr,
+                                           ws.data_ptr() if ws is not None else None, ws_n,
+                                           _stream_handle(stream, x.device))
+    _lib.check(st, "mavg_decim_run")
+
+
+def moving_average_decimated(x, grade: int, hop: int, phase: int = 0, channels: int = 1, history=None, stream=None,
+                             library: Optional[str] = None):
+    """Frames ``phase, phase + hop, ...`` of ``moving_average(x, grade)`` -- what
+    ``moving_average(x).view(-1, C)[phase::hop]`` gives -- without writing (or, for windows no
+    longer than the hop, reading) what is dropped; one launch where ``decim_plan`` says
+    ``decim_scan`` or ``decim_window``.  ``x``: ``[n]`` interleaved samples -> ``[M * channels]``,
+    or ``[frames, C]`` -> ``[M, C]``."""
+    _check_device_x(x)
+    _check_hop_phase(hop, phase)
+    frames, C = _decim_shape(x, channels)
+    M = len(range(phase, frames, hop))
+    shape = (M * C,) if x.dim() == 1 else (M, C)
+    return _with_out(x, stream, lambda out: moving_average_decimated_into(x, out, grade, hop, phase, C, history, stream,
+                                                                          library=library), (x, history), shape)
 
 
 def fill_synthetic(n: int, dtype=None, seed: int = 0x5EED, offset: int = 0, dist: int = 0,

@@ -59,6 +59,10 @@ EXPORTED_SYMBOLS = (
     "mavg_ragged_run",
     "mavg_ragged_workspace_bytes",
     "mavg_ragged_plan",
+    "mavg_decim_run",
+    "mavg_decim_out_frames",
+    "mavg_decim_workspace_bytes",
+    "mavg_decim_plan",
     "mavg_resolve_algo",
     "mavg_plan",
     "mavg_fill_synthetic",
@@ -69,7 +73,9 @@ EXPORTED_SYMBOLS = (
     "mavg_build_id",
 )
 # exported by the debug build only (include/mavg_debug.h)
-DEBUG_SYMBOLS = ("mavg_test_ahead_schedule",)
+DEBUG_SYMBOLS = ("mavg_test_ahead_schedule", "mavg_debug_force_decim")
+# mavg_debug_force_decim's paths (include/mavg_debug.h)
+DECIM_AUTO, DECIM_SCAN, DECIM_WINDOW, DECIM_FULL = 0, 1, 2, 3
 ABI_VERSION = 4
 DEBUG_LIB_PATH = os.path.join(_PKG, "lib", "libmavg_debug.so")
 # release flags + the test hooks (the forced-schedule parity tests time nothing, but they run the
@@ -124,6 +130,17 @@ def load(path: str = None) -> ctypes.CDLL:
     lib.mavg_ragged_workspace_bytes.restype = i
     lib.mavg_ragged_plan.argtypes = [i64p, sz, i, i, i, ctypes.c_char_p, sz]
     lib.mavg_ragged_plan.restype = i
+    lib.mavg_decim_run.argtypes = [vp, vp, sz, i, i, i, i, i, vp, vp, sz, vp]
+    lib.mavg_decim_run.restype = i
+    lib.mavg_decim_out_frames.argtypes = [sz, i, i, ctypes.POINTER(sz)]
+    lib.mavg_decim_out_frames.restype = i
+    lib.mavg_decim_workspace_bytes.argtypes = [sz, i, i, i, i, i, ctypes.POINTER(sz)]
+    lib.mavg_decim_workspace_bytes.restype = i
+    lib.mavg_decim_plan.argtypes = [sz, i, i, i, i, i, ctypes.c_char_p, sz]
+    lib.mavg_decim_plan.restype = i
+    if hasattr(lib, "mavg_debug_force_decim"):  # debug and hooks builds only
+        lib.mavg_debug_force_decim.argtypes = [i]
+        lib.mavg_debug_force_decim.restype = i
     lib.mavg_resolve_algo.argtypes = [sz, i, i, i, i]
     lib.mavg_resolve_algo.restype = i
     lib.mavg_plan.argtypes = [sz, i, i, i, i, i, ctypes.c_char_p, sz]

@@ -351,6 +351,110 @@ int ragged_fast_launch(const void* in, void* out, const void* d_off, size_t rows
   return ragged_scan_any(dtype, C, with_alignment(RaggedSig{in, out, d_off, rows, frames, longest}, C, dtype), k, s);
 }
 
+// ---- decimated (mavg_decim_run) -------------------------------------------------------------
+// Arguments of the decimated entry points: validate()'s for the signal, then hop and phase;
+// *out_frames = len(range(phase, frames, hop)).
+int validate_decim(size_t n, int C, int k, int hop, int phase, int dtype, size_t* out_frames) {
+  const int st = validate(n, C, k, dtype, MAVG_ALGO_AUTO, 0);
+  if (st == MAVG_ERR_INVALID_ARG) return st;
+  if (hop < 1 || phase < 0 || phase >= hop) return MAVG_ERR_INVALID_ARG;
+  if (st != MAVG_OK) return st;
+  const size_t frames = n / (size_t)C;
+  *out_frames = frames > (size_t)phase ? (frames - (size_t)phase + (size_t)hop - 1) / (size_t)hop : 0;
+  return MAVG_OK;
+}
+
+// The window sum reads k frames per output and each of them once when hop >= grade; its time goes
+// with out_frames x (a per-wave cost + the window), the scan's with the signal.  Measured with both
+// paths forced on one shape (tools/bench_decim.py --pairs, 2^30 samples, DESIGN.md "Decimated",
+// window / scan in ms, fp32 mono | int16 stereo):
+//   256-B window, hop = 4 grade: 1.29 / 1.03 | 0.93 / 0.49 (the scan's); 512 B: 0.67 / 0.96 | 0.48 / 0.47
+//   1 KiB: hop = grade 1.36 / 0.99 | 0.97 / 0.48, 1.5 grade 0.97 / 0.97 | 0.68 / 0.49, 4 grade 0.37 / 0.98 | 0.26 / 0.46
+//   2 KiB: hop = grade 0.96 / 0.97 | 0.63 / 0.47, 1.5 grade 0.69 / 0.99 | 0.43 / 0.46
+//   4 KiB: hop = grade 0.76 / 1.04 | 0.51 / 0.53, 1.5 grade 0.53 / 0.99 | 0.34 / 0.53, 2 grade 0.40 / 1.01 | 0.26 / 0.53
+//   8 KiB: hop = grade 0.69 / 1.22 | 0.35 / 0.65
+// So: windows of 4 KiB and more from hop == grade on (a win or a tie at the boundary), windows of
+// 1 KiB .. 4 KiB from hop == 2 grade on (the crossover lies between 1 and 1.5 grade at 2 KiB and
+// between 1.5 and 2 grade at 1 KiB: a margin of up to a third in hop), shorter windows never (the
+// crossover in window length lies between 256 B and 1 KiB at hop = 4 grade).
+constexpr long long kDecimWindowMinBytes = 1024;
+constexpr long long kDecimWindowHopRatio = 2;
+constexpr long long kDecimWindowDenseBytes = 4096;  // from hop == grade on
+
+// The dispatch rule for hop >= 2, in the order mavg.h gives; *path = kDecimWindow / Scan / Full.
+// The test hook's forced path replaces the rule: MAVG_ERR_UNSUPPORTED where that path cannot
+// take the shape.
+int decim_path(int C, int k, int hop, int dtype, int* path) {
+  const bool scan_ok = hop >= 2 && decim_scan_fits(dtype, C, k);
+  const bool window_can = C <= kMaxChannels;
+  int forced = kDecimAuto;
+#ifdef MAVG_TEST_HOOKS
+  forced = g_test_decim_path.load(std::memory_order_relaxed);
+#endif
+  if (forced != kDecimAuto) {
+    if ((forced == kDecimScan && !scan_ok) || (forced == kDecimWindow && !window_can)) return MAVG_ERR_UNSUPPORTED;
+    *path = forced;
+    return MAVG_OK;
+  }
+  const long long window_bytes = (long long)k * C * (long long)elem_size(dtype);
+  const bool window_ok = window_can && hop >= k && window_bytes >= kDecimWindowMinBytes;
+  if (window_ok && ((long long)hop >= kDecimWindowHopRatio * k || window_bytes >= kDecimWindowDenseBytes || !scan_ok))
+    *path = kDecimWindow;
+  else *path = scan_ok ? kDecimScan : kDecimFull;
+  return MAVG_OK;
+}
+
+struct DecimCall {
+  const void* in;
+  void* out;
+  const void* hist;
+  size_t n, out_frames;
+  int C, k, hop, phase, dtype;
+};
+
+// The one launch of decim_scan / decim_window (plan mode when g_plan is set); views of any sample
+// alignment.
+int decim_fast_launch(int path, const DecimCall& a, hipStream_t s) {
+  DecimSig ds{a.in, a.out, a.hist, a.n / (size_t)a.C, a.out_frames, a.hop, a.phase};
+  ds.unit = aligned(a.in, 16);
+  if (path == kDecimWindow) {
+    ds.eio = ds.unit ? 0 : 1;
+    return decim_window_any(a.dtype, a.C, ds, a.k, s);
+  }
+  ds.eio = !ds.unit && !aligned(a.in, elem_size(a.dtype) * (size_t)a.C) ? 1 : 0;
+  return decim_scan_any(a.dtype, a.C, ds, a.k, s);
+}
+
+// decim_full's workspace: the full-rate output (16-B padded), then mavg_run's own workspace
+int decim_full_layout(const DecimCall& a, size_t* full_bytes, size_t* inner) {
+  if (a.n > (SIZE_MAX / 4 - 15)) return MAVG_ERR_UNSUPPORTED;  // the byte count stays in size_t
+  *full_bytes = (a.n * elem_size(a.dtype) + 15) & ~(size_t)15;
+  return mavg_workspace_bytes(a.n, a.C, a.k, a.dtype, MAVG_ALGO_AUTO, 0, inner);
+}
+
+// decim_full: mavg_run (AUTO, block 0) into the workspace, then the strided gather.  Both steps
+// are planned before the first is launched: an error leaves the stream untouched.
+int decim_full_run(const DecimCall& a, void* d_ws, size_t ws_bytes, void* stream) {
+  size_t full_bytes = 0, inner = 0;
+  int st = decim_full_layout(a, &full_bytes, &inner);
+  if (st != MAVG_OK) return st;
+  st = check_workspace(full_bytes + inner, d_ws, ws_bytes);
+  if (st != MAVG_OK) return st;
+  char* const full = static_cast<char*>(d_ws);
+  void* const iws = inner > 0 ? full + full_bytes : nullptr;
+  const DecimSig ds{full, a.out, nullptr, a.n / (size_t)a.C, a.out_frames, a.hop, a.phase};
+  st = run_signal(a.in, full, a.n, a.C, a.k, a.dtype, MAVG_ALGO_AUTO, 0, a.hist, iws, inner, stream, true);
+  if (st != MAVG_OK) return st;
+  {
+    PlanScope ps;
+    st = decim_gather_any(a.dtype, a.C, full, ds, nullptr);
+    if (st != MAVG_OK) return st;
+  }
+  st = run_signal(a.in, full, a.n, a.C, a.k, a.dtype, MAVG_ALGO_AUTO, 0, a.hist, iws, inner, stream, false);
+  if (st != MAVG_OK) return st;
+  return decim_gather_any(a.dtype, a.C, full, ds, static_cast<hipStream_t>(stream));
+}
+
 }  // namespace
 
 extern "C" {
@@ -530,6 +634,88 @@ int mavg_rows_run(const void* d_in, void* d_out, size_t rows, size_t row_frames,
                       row_samples, channels, grade, dtype, MAVG_ALGO_AUTO, 0, h, d_ws, ws_bytes, stream, dry);
   };
   return run_row_loop(rows, rows_alignment_period(rows), row_samples, channels, grade, dtype, d_ws, ws_bytes, row_run);
+}
+
+int mavg_decim_out_frames(size_t n_frames, int hop, int phase, size_t* out_frames) {
+  if (out_frames == nullptr || hop < 1 || phase < 0 || phase >= hop) return MAVG_ERR_INVALID_ARG;
+  *out_frames = n_frames > (size_t)phase ? (n_frames - (size_t)phase - 1) / (size_t)hop + 1 : 0;
+  return MAVG_OK;
+}
+
+int mavg_decim_workspace_bytes(size_t n_samples, int channels, int grade, int hop, int phase, int dtype,
+                               size_t* out_bytes) {
+  if (out_bytes == nullptr) return MAVG_ERR_INVALID_ARG;
+  size_t M = 0;
+  int st = validate_decim(n_samples, channels, grade, hop, phase, dtype, &M);
+  if (st != MAVG_OK) return st;
+  *out_bytes = 0;
+  if (M == 0) return MAVG_OK;
+  if (hop == 1) return mavg_workspace_bytes(n_samples, channels, grade, dtype, MAVG_ALGO_AUTO, 0, out_bytes);
+  int path = kDecimFull;
+  st = decim_path(channels, grade, hop, dtype, &path);
+  if (st != MAVG_OK) return st;
+  const DecimCall a{kPlanIn, kPlanOut, nullptr, n_samples, M, channels, grade, hop, phase, dtype};
+  if (path != kDecimFull) {
+    // no workspace; the launch's own limit (grid_too_large) shows here as it does in mavg_decim_run
+    PlanScope ps;
+    return decim_fast_launch(path, a, nullptr);
+  }
+  size_t full_bytes = 0, inner = 0;
+  st = decim_full_layout(a, &full_bytes, &inner);
+  if (st != MAVG_OK) return st;
+  *out_bytes = full_bytes + inner;
+  return MAVG_OK;
+}
+
+int mavg_decim_plan(size_t n_samples, int channels, int grade, int hop, int phase, int dtype, char* buf,
+                    size_t buflen) {
+  if (buf == nullptr || buflen == 0) return MAVG_ERR_INVALID_ARG;
+  buf[0] = 0;
+  size_t M = 0;
+  int st = validate_decim(n_samples, channels, grade, hop, phase, dtype, &M);
+  if (st != MAVG_OK) return st;
+  if (M == 0) return MAVG_ERR_INVALID_ARG;  // nothing to describe, as mavg_plan
+  int path = kDecimFull;
+  if (hop > 1) {
+    st = decim_path(channels, grade, hop, dtype, &path);
+    if (st != MAVG_OK) return st;
+    if (path != kDecimFull) {
+      PlanScope ps;
+      st = decim_fast_launch(path, DecimCall{kPlanIn, kPlanOut, nullptr, n_samples, M, channels, grade, hop, phase, dtype},
+                             nullptr);
+      if (st == MAVG_OK) snprintf(buf, buflen, "%s", ps.plan.text);
+      return st;
+    }
+  }
+  char full[sizeof(LaunchPlan::text)];
+  st = mavg_plan(n_samples, channels, grade, dtype, MAVG_ALGO_AUTO, 0, full, sizeof(full));
+  if (st != MAVG_OK) return st;
+  if (hop == 1) snprintf(buf, buflen, "decim_none x %s", full);
+  else snprintf(buf, buflen, "decim_full hop=%d phase=%d x %s", hop, phase, full);
+  return MAVG_OK;
+}
+
+// hop == 1: mavg_run itself.  Else one launch of the compacting scan or of the window sum where the
+// rule (decim_path) takes them, else mavg_run into the workspace and a gather, both planned first.
+int mavg_decim_run(const void* d_in, void* d_out, size_t n_samples, int channels, int grade, int hop, int phase,
+                   int dtype, const void* d_history, void* d_ws, size_t ws_bytes, void* stream) {
+  size_t M = 0;
+  int st = validate_decim(n_samples, channels, grade, hop, phase, dtype, &M);
+  if (st != MAVG_OK) return st;
+  if (M == 0) return MAVG_OK;
+  if (d_in == nullptr || d_out == nullptr) return MAVG_ERR_INVALID_ARG;
+  const size_t eb = elem_size(dtype);
+  if (!aligned(d_in, eb) || !aligned(d_out, eb) || (d_history != nullptr && !aligned(d_history, eb)))
+    return MAVG_ERR_MISALIGNED;
+  if (hop == 1)
+    return run_signal(d_in, d_out, n_samples, channels, grade, dtype, MAVG_ALGO_AUTO, 0, d_history, d_ws, ws_bytes,
+                      stream, false);
+  int path = kDecimFull;
+  st = decim_path(channels, grade, hop, dtype, &path);
+  if (st != MAVG_OK) return st;
+  const DecimCall a{d_in, d_out, d_history, n_samples, M, channels, grade, hop, phase, dtype};
+  if (path != kDecimFull) return decim_fast_launch(path, a, static_cast<hipStream_t>(stream));
+  return decim_full_run(a, d_ws, ws_bytes, stream);
 }
 
 int mavg_ragged_workspace_bytes(const int64_t* h_offsets, size_t rows, int channels, int grade, int dtype,

@@ -8,6 +8,7 @@ thread_local LaunchPlan* g_plan = nullptr;
 #ifdef MAVG_TEST_HOOKS
 std::atomic<int> g_test_ahead_slots{-1};
 std::atomic<int> g_test_ahead_spin{-1};
+std::atomic<int> g_test_decim_path{kDecimAuto};
 #endif
 
 // ---- per-device attribute cache (no stream work, capture-safe) --------------
@@ -46,6 +47,11 @@ OutParams make_out_params(int k) {
 extern "C" int mavg_test_ahead_schedule(int slots, int spin) {
   mavg::g_test_ahead_slots.store(slots < 0 ? -1 : std::min(slots, 1 << 30), std::memory_order_relaxed);
   mavg::g_test_ahead_spin.store(spin < 0 ? -1 : std::min(spin, 1 << 20), std::memory_order_relaxed);
+  return MAVG_OK;
+}
+extern "C" int mavg_debug_force_decim(int path) {
+  if (path < mavg::kDecimAuto || path > mavg::kDecimFull) return MAVG_ERR_INVALID_ARG;
+  mavg::g_test_decim_path.store(path, std::memory_order_relaxed);
   return MAVG_OK;
 }
 #endif

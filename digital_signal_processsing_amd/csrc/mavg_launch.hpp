@@ -189,6 +189,38 @@ bool ragged_scan_fits(int dtype, int C, size_t max_row_frames, int grade);
 // MAVG_ERR_UNSUPPORTED: the halo does not fit, or the launch would exceed grid_too_large
 int ragged_scan_any(int dtype, int C, const RaggedSig& rs, int grade, hipStream_t st);
 
+// The decimated moving average (mavg_decim.hpp, instantiated in mavg_decim.hip): out_frames =
+// len(range(phase, nframes, hop)) output frames, packed.
+//   unit  the scan's 16-B-unit form (the input 16-B aligned); else its frame-unit (F = 1) form
+//   eio   the scan: frame-unit form on an input that is only element-aligned (UnitIO::gload);
+//         the window sum: the input is not 16-B aligned (no 16-B loads)
+// The output may be any sample-aligned view in every form.
+struct DecimSig {
+  const void* in;
+  void* out;
+  const void* hist;
+  size_t nframes;
+  size_t out_frames;
+  int hop;
+  int phase;
+  bool unit = true;
+  int eio = 0;
+};
+// The test hook's forced path (mavg_debug_force_decim, include/mavg_debug.h): 0 = the rule decides
+constexpr int kDecimAuto = 0, kDecimScan = 1, kDecimWindow = 2, kDecimFull = 3;
+#ifdef MAVG_TEST_HOOKS
+extern std::atomic<int> g_test_decim_path;
+#endif
+// Whether the compacting scan takes this window: channels 1 or 2, grade >= 2, int16 grade <= 65535,
+// a halo of at most 8 KiB, and its LDS layout (DecimLds) inside lds_budget in both forms.
+bool decim_scan_fits(int dtype, int C, int grade);
+// MAVG_ERR_UNSUPPORTED: hop < 2, the window does not fit, or the launch would exceed grid_too_large
+int decim_scan_any(int dtype, int C, const DecimSig& ds, int grade, hipStream_t st);
+// one wave per output frame; channels 1..8 (else MAVG_ERR_UNSUPPORTED), every grade and hop
+int decim_window_any(int dtype, int C, const DecimSig& ds, int grade, hipStream_t st);
+// out = the frames phase + m * hop of the full-rate signal `full` (ds.in is not read)
+int decim_gather_any(int dtype, int C, const void* full, const DecimSig& ds, hipStream_t st);
+
 // ceil(k / F): the units a k-frame halo takes (TileParams / AheadParams halo_units)
 template <int F>
 constexpr size_t tile_halo_units(int k) { return (size_t)(((long long)k + F - 1) / F); }

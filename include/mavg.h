@@ -273,6 +273,80 @@ int mavg_ragged_workspace_bytes(const int64_t* h_offsets, size_t rows, int chann
 int mavg_ragged_plan(const int64_t* h_offsets, size_t rows, int channels, int grade,
                      int dtype, char* buf, size_t buflen);
 
+/*
+ * Decimated moving average: of mavg_run's full-rate output only the frames
+ * phase + m * hop, m in [0, M), M = len(range(phase, n_frames, hop)), packed:
+ * d_out holds M * channels samples.  hop >= 1, 0 <= phase < hop; phase counts
+ * from d_in's frame 0, whatever the history.  Everything else is mavg_run's
+ * contract: interleaved channels, zero history or d_history (the
+ * (grade-1)*channels samples in front of d_in), divisor grade, int16 exact
+ * truncating division, fp32 sums in fp64.  What a caller otherwise does with
+ * mavg_run and y.view(-1, C)[phase::hop], without writing (or, for sparse
+ * windows, reading) what is dropped.
+ *   d_in   any sample-aligned view of n_samples samples; one that is not 16-B
+ *          aligned runs the scan's one-frame-per-lane form (no head is peeled).
+ *   d_out  any sample-aligned view of M * channels samples.
+ *   d_ws   mavg_decim_workspace_bytes() bytes, 16-B aligned (NULL when 0).
+ * Ownership, stream and capture rules are mavg_run's: no allocation, no
+ * synchronisation, nothing enqueued unless MAVG_OK is returned (MAVG_ERR_HIP
+ * excepted).  M == 0 (n_samples == 0, or n_frames <= phase): MAVG_OK, nothing
+ * enqueued.
+ *
+ * Status: MAVG_ERR_INVALID_ARG for hop < 1, phase outside [0, hop) and
+ * mavg_run's invalid cases; MAVG_ERR_MISALIGNED, MAVG_ERR_WORKSPACE and
+ * MAVG_ERR_UNSUPPORTED as mavg_run.
+ *
+ * Dispatch, evaluated in this order (mavg_decim_plan shows which):
+ *   decim_none    hop == 1: mavg_run (MAVG_ALGO_AUTO, block_size 0), unchanged.
+ *   decim_window  sparse reading, ONE launch, no workspace: channels <= 8,
+ *                 hop >= grade, a window of at least 1 KiB (grade * channels *
+ *                 sample size >= 1024), and one of: hop >= 2 * grade, a window
+ *                 of at least 4 KiB, decim_scan does not apply (the measured
+ *                 crossovers, DESIGN.md "Decimated").  One wave per output frame sums
+ *                 the grade frames that output needs, each read once, in fp64
+ *                 (fp32) or int64 (int16): exact for every grade.
+ *   decim_scan    dense reading, ONE launch, no workspace: hop >= 2, channels 1
+ *                 or 2, 2 <= grade (int16: <= 65535), a halo of grade * channels
+ *                 * sample size <= 8 KiB (half of rows_scan's range: at 16 KiB
+ *                 it measured slower than mavg_run and a slice).  The flat tile
+ *                 scan with a compacting end: every input frame is read, only
+ *                 the kept frames are converted and stored.  Any hop, also
+ *                 hop >= grade with a window under 1 KiB (block averaging).
+ *   decim_full    everything else (3+ channels with a short or overlapping
+ *                 window, longer halos with hop < grade, int16 grade > 65535
+ *                 with hop < grade, grade == 1): mavg_run (AUTO) into the
+ *                 workspace, then a strided gather -- correct, not fast.  Both
+ *                 steps are planned before the first is launched: an error
+ *                 leaves the stream untouched.
+ *
+ * Supported maximum.  mavg_run's: every kernel makes one launch
+ * (decim_scan: `block` threads per `tile_frames` frames, decim_window: one wave
+ * per output frame), past it MAVG_ERR_UNSUPPORTED and nothing is enqueued.
+ * NOT tested past 2^31 samples (frame and sample indices that are not
+ * tile-local are 64-bit in the kernels).
+ */
+int mavg_decim_run(const void* d_in, void* d_out, size_t n_samples, int channels, int grade,
+                   int hop, int phase, int dtype, const void* d_history,
+                   void* d_ws, size_t ws_bytes, void* stream);
+
+/* M = len(range(phase, n_frames, hop)): the frames mavg_decim_run writes. */
+int mavg_decim_out_frames(size_t n_frames, int hop, int phase, size_t* out_frames);
+
+/* Device workspace (bytes) mavg_decim_run needs: 0 for decim_scan and
+ * decim_window; mavg_workspace_bytes for decim_none; for decim_full the
+ * full-rate output, n_samples * sample size rounded up to 16, plus
+ * mavg_workspace_bytes for the full-rate run. */
+int mavg_decim_workspace_bytes(size_t n_samples, int channels, int grade, int hop, int phase,
+                               int dtype, size_t* out_bytes);
+
+/* Describe, without launching anything, what mavg_decim_run would do on
+ * 16-B-aligned views: "decim_none x <mavg_plan's text>", "decim_window<...> ...",
+ * "decim_scan<...> ... tile_frames=N ..." or "decim_full hop=H phase=P x
+ * <mavg_plan's text>" (up to ~300 characters).  M == 0 has no plan:
+ * MAVG_ERR_INVALID_ARG. */
+int mavg_decim_plan(size_t n_samples, int channels, int grade, int hop, int phase, int dtype,
+                    char* buf, size_t buflen);
+
 /* Describe, without launching anything, the kernel and launch geometry
  * mavg_run would use for these arguments on 16-B-aligned views
  * (e.g. "tile_scan<f32,...> grid=... block=256 ..."). */

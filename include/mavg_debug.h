@@ -27,6 +27,16 @@ extern "C" {
  * returns MAVG_OK. */
 int mavg_test_ahead_schedule(int slots, int spin);
 
+/* TEST HOOK (parity tests and tools/bench_decim.py): force mavg_decim_run's path
+ * for hop >= 2 -- 0: the dispatch rule decides (the default), 1: decim_scan,
+ * 2: decim_window, 3: decim_full -- so that two paths can run on one shape.  A
+ * forced path that cannot take the shape (decim_scan outside its range,
+ * decim_window with more than 8 channels) makes mavg_decim_run, mavg_decim_plan
+ * and mavg_decim_workspace_bytes return MAVG_ERR_UNSUPPORTED; hop == 1 stays
+ * decim_none.  Process-wide, like the schedule hook; returns MAVG_OK, or
+ * MAVG_ERR_INVALID_ARG for another value (nothing changes). */
+int mavg_debug_force_decim(int path);
+
 #ifdef __cplusplus
 }
 #endif
