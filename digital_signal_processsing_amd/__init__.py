@@ -40,6 +40,10 @@ __all__ = [
     "decim_out_frames",
     "decim_plan",
     "decim_workspace_bytes",
+    "moving_average_cascade",
+    "moving_average_cascade_into",
+    "cascade_plan",
+    "cascade_workspace_bytes",
     "fill_synthetic",
     "workspace_bytes",
     "resolve_algo",
@@ -549,6 +553,75 @@ def moving_average_decimated(x, grade: int, hop: int, phase: int = 0, channels: 
     shape = (M * C,) if x.dim() == 1 else (M, C)
     return _with_out(x, stream, lambda out: moving_average_decimated_into(x, out, grade, hop, phase, C, history, stream,
                                                                           library=library), (x, history), shape)
+
+
+def _check_passes(passes: int) -> None:
+    if passes < 1:
+        raise ValueError(f"passes must be >= 1, got {passes}")
+
+
+def cascade_workspace_bytes(n: int, grade: int, passes: int, channels: int = 1, dtype: int = F32,
+                            with_history: bool = False, library: Optional[str] = None) -> int:
+    """Device workspace ``moving_average_cascade_into`` needs: 0 for the one-launch fused kernel
+    (``cascade_tile``), ``workspace_bytes`` for ``passes == 1``, and for ``cascade_loop`` the
+    ping-pong buffer, with a history two history-block buffers, plus ``workspace_bytes``."""
+    import ctypes
+    _check_passes(passes)
+    out = ctypes.c_size_t(0)
+    _lib.check(_lib.load(library).mavg_cascade_workspace_bytes(n, channels, grade, passes, dtype, int(bool(with_history)),
+                                                               ctypes.byref(out)), "mavg_cascade_workspace_bytes")
+    return out.value
+
+
+def cascade_plan(n: int, grade: int, passes: int, channels: int = 1, dtype: int = F32, with_history: bool = False,
+                 library: Optional[str] = None) -> str:
+    """What mavg_cascade_run would do (nothing is launched): ``cascade_none x <plan>``,
+    ``cascade_tile<...> ... tile_frames=N ...`` or ``cascade_loop passes=P history=0|1 x <plan>``."""
+    import ctypes
+    _check_passes(passes)
+    buf = ctypes.create_string_buffer(512)
+    _lib.check(_lib.load(library).mavg_cascade_plan(n, channels, grade, passes, dtype, int(bool(with_history)), buf,
+                                                    len(buf)), "mavg_cascade_plan")
+    return buf.value.decode()
+
+
+def moving_average_cascade_into(x, out, grade: int, passes: int, channels: int = 1, history=None, stream=None,
+                                workspace=None, library: Optional[str] = None) -> None:
+    """Enqueue ``out = moving_average_cascade(x)`` on ``stream`` (default: current).
+
+    ``out``: a contiguous device tensor of ``x``'s size that does not overlap ``x``.  ``history``:
+    the ``passes * (grade-1) * channels`` samples in front of ``x``.  ``workspace``: as in
+    ``moving_average_rows_into``; only the loop (and ``passes == 1`` at long windows) needs one
+    (``cascade_workspace_bytes``)."""
+    _check_passes(passes)
+    frames, C = _decim_shape(x, channels)
+    if x.dtype != out.dtype:
+        raise ValueError("x and out must have the same dtype")
+    if out.numel() != x.numel():
+        raise ValueError(f"out must hold x's {x.numel()} samples, got {out.numel()}")
+    _check_device_pair(x, out)
+    dt = _dtype_code(x)
+    hist_ptr = _history_ptr(history, x, passes * (grade - 1) * C, "passes*(grade-1)*channels")
+    ws_n = cascade_workspace_bytes(x.numel(), grade, passes, C, dt, history is not None, library)
+    ws, ws_n = _loop_workspace(ws_n, workspace, stream, x.device, "cascade_workspace_bytes")
+    st = _lib.load(library).mavg_cascade_run(x.data_ptr(), out.data_ptr(), x.numel(), C, grade, passes, dt, hist_ptr,
+                                             ws.data_ptr() if ws is not None else None, ws_n,
+                                             _stream_handle(stream, x.device))
+    _lib.check(st, "mavg_cascade_run")
+
+
+def moving_average_cascade(x, grade: int, passes: int, channels: int = 1, history=None, stream=None,
+                           library: Optional[str] = None):
+    """``passes`` successive ``moving_average(x, grade)`` passes with zero history (two: a
+    triangular window; three or four: the usual Gaussian approximation), the intermediate kept in
+    ``x``'s dtype; one launch where ``cascade_plan`` says ``cascade_tile``.  ``x``: ``[n]``
+    interleaved samples or ``[frames, C]``; the result has ``x``'s shape."""
+    _check_device_x(x)
+    _check_passes(passes)
+    _decim_shape(x, channels)
+    C = channels if x.dim() == 1 else x.shape[1]
+    return _with_out(x, stream, lambda out: moving_average_cascade_into(x, out, grade, passes, C, history, stream,
+                                                                        library=library), (x, history))
 
 
 def fill_synthetic(n: int, dtype=None, seed: int = 0x5EED, offset: int = 0, dist: int = 0,

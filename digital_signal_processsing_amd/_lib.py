@@ -63,6 +63,9 @@ EXPORTED_SYMBOLS = (
     "mavg_decim_out_frames",
     "mavg_decim_workspace_bytes",
     "mavg_decim_plan",
+    "mavg_cascade_run",
+    "mavg_cascade_workspace_bytes",
+    "mavg_cascade_plan",
     "mavg_resolve_algo",
     "mavg_plan",
     "mavg_fill_synthetic",
@@ -73,9 +76,11 @@ EXPORTED_SYMBOLS = (
     "mavg_build_id",
 )
 # exported by the debug build only (include/mavg_debug.h)
-DEBUG_SYMBOLS = ("mavg_test_ahead_schedule", "mavg_debug_force_decim")
+DEBUG_SYMBOLS = ("mavg_test_ahead_schedule", "mavg_debug_force_decim", "mavg_debug_force_cascade")
 # mavg_debug_force_decim's paths (include/mavg_debug.h)
 DECIM_AUTO, DECIM_SCAN, DECIM_WINDOW, DECIM_FULL = 0, 1, 2, 3
+# mavg_debug_force_cascade's paths (include/mavg_debug.h)
+CASCADE_AUTO, CASCADE_TILE, CASCADE_LOOP = 0, 1, 2
 ABI_VERSION = 4
 DEBUG_LIB_PATH = os.path.join(_PKG, "lib", "libmavg_debug.so")
 # release flags + the test hooks (the forced-schedule parity tests time nothing, but they run the
@@ -141,6 +146,15 @@ def load(path: str = None) -> ctypes.CDLL:
     if hasattr(lib, "mavg_debug_force_decim"):  # debug and hooks builds only
         lib.mavg_debug_force_decim.argtypes = [i]
         lib.mavg_debug_force_decim.restype = i
+    lib.mavg_cascade_run.argtypes = [vp, vp, sz, i, i, i, i, vp, vp, sz, vp]
+    lib.mavg_cascade_run.restype = i
+    lib.mavg_cascade_workspace_bytes.argtypes = [sz, i, i, i, i, i, ctypes.POINTER(sz)]
+    lib.mavg_cascade_workspace_bytes.restype = i
+    lib.mavg_cascade_plan.argtypes = [sz, i, i, i, i, i, ctypes.c_char_p, sz]
+    lib.mavg_cascade_plan.restype = i
+    if hasattr(lib, "mavg_debug_force_cascade"):  # debug and hooks builds only
+        lib.mavg_debug_force_cascade.argtypes = [i]
+        lib.mavg_debug_force_cascade.restype = i
     lib.mavg_resolve_algo.argtypes = [sz, i, i, i, i]
     lib.mavg_resolve_algo.restype = i
     lib.mavg_plan.argtypes = [sz, i, i, i, i, i, ctypes.c_char_p, sz]

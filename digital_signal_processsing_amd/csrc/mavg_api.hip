@@ -455,6 +455,111 @@ int decim_full_run(const DecimCall& a, void* d_ws, size_t ws_bytes, void* stream
   return decim_gather_any(a.dtype, a.C, full, ds, static_cast<hipStream_t>(stream));
 }
 
+// ---- cascaded (mavg_cascade_run) ------------------------------------------------------------
+// Arguments of the cascaded entry points: validate()'s for the signal, then passes; the total
+// halo passes * (grade - 1) frames must stay in int.
+int validate_cascade(size_t n, int C, int k, int passes, int dtype) {
+  const int st = validate(n, C, k, dtype, MAVG_ALGO_AUTO, 0);
+  if (st == MAVG_ERR_INVALID_ARG) return st;
+  if (passes < 1) return MAVG_ERR_INVALID_ARG;
+  if (st != MAVG_OK) return st;
+  if ((long long)passes * (long long)(k - 1) > 0x7fffffffLL) return MAVG_ERR_UNSUPPORTED;
+  return MAVG_OK;
+}
+
+// The dispatch rule past cascade_none, in the order mavg.h gives; *path = kCascadeTile / Loop: the
+// fused kernel where it can take the cascade (cascade_tile_fits) and measured faster
+// (cascade_tile_preferred).  The test hook's forced path replaces the rule: MAVG_ERR_UNSUPPORTED
+// where the kernel cannot take the shape.
+int cascade_path(int C, int k, int passes, int dtype, int* path) {
+  const bool tile_ok = cascade_tile_fits(dtype, C, k, passes);
+  int forced = kCascadeAuto;
+#ifdef MAVG_TEST_HOOKS
+  forced = g_test_cascade_path.load(std::memory_order_relaxed);
+#endif
+  if (forced == kCascadeTile && !tile_ok) return MAVG_ERR_UNSUPPORTED;
+  const bool rule = tile_ok && cascade_tile_preferred(dtype, C, k, passes);
+  *path = forced != kCascadeAuto ? forced : rule ? kCascadeTile : kCascadeLoop;
+  return MAVG_OK;
+}
+
+struct CascadeCall {
+  const void* in;
+  void* out;
+  const void* hist;
+  size_t n;
+  int C, k, passes, dtype;
+};
+
+// The one launch of cascade_tile (plan mode when g_plan is set); views of any sample alignment.
+int cascade_tile_launch(const CascadeCall& a, hipStream_t s) {
+  CascadeSig cs{a.in, a.out, a.hist, a.n / (size_t)a.C};
+  cs.unit = aligned(a.in, 16) && aligned(a.out, 16);
+  cs.eio = !cs.unit && !aligned(a.in, elem_size(a.dtype) * (size_t)a.C) ? 1 : 0;
+  return cascade_tile_any(a.dtype, a.C, cs, a.k, a.passes, s);
+}
+
+// cascade_loop's workspace, in this order: the ping-pong buffer (the signal's bytes, 16-B padded);
+// with a history two block buffers of passes * (grade - 1) * C samples each (16-B padded); then
+// mavg_run's own workspace -- the signal's, and with a history at least the first block's.
+struct CascadeLoopLayout {
+  size_t pong, block, inner;
+  size_t bytes() const { return pong + 2 * block + inner; }
+};
+int cascade_loop_layout(const CascadeCall& a, bool with_history, CascadeLoopLayout* l) {
+  if (a.n > (SIZE_MAX / 4 - 15)) return MAVG_ERR_UNSUPPORTED;  // the byte count stays in size_t
+  const size_t eb = elem_size(a.dtype);
+  l->pong = (a.n * eb + 15) & ~(size_t)15;
+  l->block = 0;
+  int st = mavg_workspace_bytes(a.n, a.C, a.k, a.dtype, MAVG_ALGO_AUTO, 0, &l->inner);
+  if (st != MAVG_OK || !with_history) return st;
+  const size_t hs = (size_t)a.passes * (size_t)(a.k - 1) * (size_t)a.C;  // < 2^31 * 8 (validate_cascade, C <= 8 or naive)
+  if (hs > (SIZE_MAX / 4 - 15)) return MAVG_ERR_UNSUPPORTED;
+  l->block = (hs * eb + 15) & ~(size_t)15;
+  size_t hin = 0;
+  st = mavg_workspace_bytes(hs, a.C, a.k, a.dtype, MAVG_ALGO_AUTO, 0, &hin);
+  l->inner = std::max(l->inner, hin);
+  return st;
+}
+
+// cascade_loop: `passes` mavg_run calls (AUTO, block 0), never in place, between d_out and the
+// ping-pong buffer so that the last lands in d_out.  With a history, pass j first filters block
+// j - 1 (block 0 is the caller's history; zero history, the first grade - 1 outputs dropped) into
+// block j, the history of pass j + 1; pass j itself takes the last grade - 1 frames of block j - 1.
+// Every step is made dry first: an error leaves the stream untouched.
+int cascade_loop_run(const CascadeCall& a, void* d_ws, size_t ws_bytes, void* stream) {
+  CascadeLoopLayout l{};
+  int st = cascade_loop_layout(a, a.hist != nullptr, &l);
+  if (st != MAVG_OK) return st;
+  st = check_workspace(l.bytes(), d_ws, ws_bytes);
+  if (st != MAVG_OK) return st;
+  char* const pong = static_cast<char*>(d_ws);
+  char* const blocks[2] = {pong + l.pong, pong + l.pong + l.block};
+  void* const iws = l.inner > 0 ? pong + l.pong + 2 * l.block : nullptr;
+  const size_t fb = elem_size(a.dtype) * (size_t)a.C;
+  const size_t km1 = (size_t)(a.k - 1);
+  for (int dry = 1; dry >= 0; --dry) {
+    const void* src = a.in;
+    const char* blk = static_cast<const char*>(a.hist);  // block j - 1: (passes - j + 1)(k - 1) frames
+    for (int j = 1; j <= a.passes; ++j) {
+      void* const dst = ((a.passes - j) & 1) ? static_cast<void*>(pong) : a.out;
+      const size_t bframes = (size_t)(a.passes - j + 1) * km1;
+      const void* h = blk != nullptr ? blk + (bframes - km1) * fb : nullptr;
+      st = run_signal(src, dst, a.n, a.C, a.k, a.dtype, MAVG_ALGO_AUTO, 0, h, iws, l.inner, stream, dry != 0);
+      if (st != MAVG_OK) return st;
+      if (blk != nullptr && j < a.passes) {
+        char* const nb = blocks[(j - 1) & 1];
+        st = run_signal(blk, nb, bframes * (size_t)a.C, a.C, a.k, a.dtype, MAVG_ALGO_AUTO, 0, nullptr, iws, l.inner,
+                        stream, dry != 0);
+        if (st != MAVG_OK) return st;
+        blk = nb + km1 * fb;
+      }
+      src = dst;
+    }
+  }
+  return MAVG_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -716,6 +821,81 @@ int mavg_decim_run(const void* d_in, void* d_out, size_t n_samples, int channels
   const DecimCall a{d_in, d_out, d_history, n_samples, M, channels, grade, hop, phase, dtype};
   if (path != kDecimFull) return decim_fast_launch(path, a, static_cast<hipStream_t>(stream));
   return decim_full_run(a, d_ws, ws_bytes, stream);
+}
+
+int mavg_cascade_workspace_bytes(size_t n_samples, int channels, int grade, int passes, int dtype, int with_history,
+                                 size_t* out_bytes) {
+  if (out_bytes == nullptr) return MAVG_ERR_INVALID_ARG;
+  int st = validate_cascade(n_samples, channels, grade, passes, dtype);
+  if (st != MAVG_OK) return st;
+  *out_bytes = 0;
+  if (n_samples == 0) return MAVG_OK;
+  if (passes == 1 || grade == 1)
+    return mavg_workspace_bytes(n_samples, channels, grade, dtype, MAVG_ALGO_AUTO, 0, out_bytes);
+  int path = kCascadeLoop;
+  st = cascade_path(channels, grade, passes, dtype, &path);
+  if (st != MAVG_OK) return st;
+  const CascadeCall a{kPlanIn, kPlanOut, nullptr, n_samples, channels, grade, passes, dtype};
+  if (path == kCascadeTile) {
+    // no workspace; the launch's own limit (grid_too_large) shows here as it does in mavg_cascade_run
+    PlanScope ps;
+    return cascade_tile_launch(a, nullptr);
+  }
+  CascadeLoopLayout l{};
+  st = cascade_loop_layout(a, with_history != 0, &l);
+  if (st != MAVG_OK) return st;
+  *out_bytes = l.bytes();
+  return MAVG_OK;
+}
+
+int mavg_cascade_plan(size_t n_samples, int channels, int grade, int passes, int dtype, int with_history, char* buf,
+                      size_t buflen) {
+  if (buf == nullptr || buflen == 0) return MAVG_ERR_INVALID_ARG;
+  buf[0] = 0;
+  int st = validate_cascade(n_samples, channels, grade, passes, dtype);
+  if (st != MAVG_OK) return st;
+  if (n_samples == 0) return MAVG_ERR_INVALID_ARG;  // nothing to describe, as mavg_plan
+  const bool none = passes == 1 || grade == 1;
+  if (!none) {
+    int path = kCascadeLoop;
+    st = cascade_path(channels, grade, passes, dtype, &path);
+    if (st != MAVG_OK) return st;
+    if (path == kCascadeTile) {
+      PlanScope ps;
+      st = cascade_tile_launch(CascadeCall{kPlanIn, kPlanOut, nullptr, n_samples, channels, grade, passes, dtype}, nullptr);
+      if (st == MAVG_OK) snprintf(buf, buflen, "%s", ps.plan.text);
+      return st;
+    }
+  }
+  char one[sizeof(LaunchPlan::text)];
+  st = mavg_plan(n_samples, channels, grade, dtype, MAVG_ALGO_AUTO, 0, one, sizeof(one));
+  if (st != MAVG_OK) return st;
+  if (none) snprintf(buf, buflen, "cascade_none x %s", one);
+  else snprintf(buf, buflen, "cascade_loop passes=%d history=%d x %s", passes, with_history != 0 ? 1 : 0, one);
+  return MAVG_OK;
+}
+
+// passes == 1 or grade == 1: mavg_run itself.  Else one launch of the fused tile kernel where the
+// rule (cascade_path) takes it, else `passes` mavg_run calls through the workspace, all planned
+// first.
+int mavg_cascade_run(const void* d_in, void* d_out, size_t n_samples, int channels, int grade, int passes, int dtype,
+                     const void* d_history, void* d_ws, size_t ws_bytes, void* stream) {
+  int st = validate_cascade(n_samples, channels, grade, passes, dtype);
+  if (st != MAVG_OK) return st;
+  if (n_samples == 0) return MAVG_OK;
+  if (d_in == nullptr || d_out == nullptr) return MAVG_ERR_INVALID_ARG;
+  const size_t eb = elem_size(dtype);
+  if (!aligned(d_in, eb) || !aligned(d_out, eb) || (d_history != nullptr && !aligned(d_history, eb)))
+    return MAVG_ERR_MISALIGNED;
+  if (passes == 1 || grade == 1)
+    return run_signal(d_in, d_out, n_samples, channels, grade, dtype, MAVG_ALGO_AUTO, 0, d_history, d_ws, ws_bytes,
+                      stream, false);
+  int path = kCascadeLoop;
+  st = cascade_path(channels, grade, passes, dtype, &path);
+  if (st != MAVG_OK) return st;
+  const CascadeCall a{d_in, d_out, d_history, n_samples, channels, grade, passes, dtype};
+  if (path == kCascadeTile) return cascade_tile_launch(a, static_cast<hipStream_t>(stream));
+  return cascade_loop_run(a, d_ws, ws_bytes, stream);
 }
 
 int mavg_ragged_workspace_bytes(const int64_t* h_offsets, size_t rows, int channels, int grade, int dtype,

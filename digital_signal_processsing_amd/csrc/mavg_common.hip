@@ -9,6 +9,7 @@ thread_local LaunchPlan* g_plan = nullptr;
 std::atomic<int> g_test_ahead_slots{-1};
 std::atomic<int> g_test_ahead_spin{-1};
 std::atomic<int> g_test_decim_path{kDecimAuto};
+std::atomic<int> g_test_cascade_path{kCascadeAuto};
 #endif
 
 // ---- per-device attribute cache (no stream work, capture-safe) --------------
@@ -52,6 +53,11 @@ extern "C" int mavg_test_ahead_schedule(int slots, int spin) {
 extern "C" int mavg_debug_force_decim(int path) {
   if (path < mavg::kDecimAuto || path > mavg::kDecimFull) return MAVG_ERR_INVALID_ARG;
   mavg::g_test_decim_path.store(path, std::memory_order_relaxed);
+  return MAVG_OK;
+}
+extern "C" int mavg_debug_force_cascade(int path) {
+  if (path < mavg::kCascadeAuto || path > mavg::kCascadeLoop) return MAVG_ERR_INVALID_ARG;
+  mavg::g_test_cascade_path.store(path, std::memory_order_relaxed);
   return MAVG_OK;
 }
 #endif

@@ -221,6 +221,34 @@ int decim_window_any(int dtype, int C, const DecimSig& ds, int grade, hipStream_
 // out = the frames phase + m * hop of the full-rate signal `full` (ds.in is not read)
 int decim_gather_any(int dtype, int C, const void* full, const DecimSig& ds, hipStream_t st);
 
+// The cascaded moving average (mavg_cascade.hpp, instantiated in mavg_cascade.hip): `passes` boxcar
+// passes of one window in one launch; hist holds passes * (grade - 1) frames or is NULL.
+//   unit  the 16-B-unit form (both views 16-B aligned); else the frame-unit (F = 1) form
+//   eio   frame-unit form on an input that is only element-aligned (UnitIO::gload)
+struct CascadeSig {
+  const void* in;
+  void* out;
+  const void* hist;
+  size_t nframes;
+  bool unit = true;
+  int eio = 0;
+};
+// The test hook's forced path (mavg_debug_force_cascade, include/mavg_debug.h): 0 = the rule decides
+constexpr int kCascadeAuto = 0, kCascadeTile = 1, kCascadeLoop = 2;
+#ifdef MAVG_TEST_HOOKS
+extern std::atomic<int> g_test_cascade_path;
+#endif
+// Whether the fused kernel CAN take this cascade (and a forced cascade_tile may run it): channels 1
+// or 2, grade >= 2, passes >= 2, int16 grade <= 65535, a total halo passes * (grade - 1) * C *
+// sample size of at most 16 KiB, and its LDS layout (CascadeLds) inside lds_budget in both forms.
+// passes * (grade - 1) must not overflow int (mavg_api.hip).
+bool cascade_tile_fits(int dtype, int C, int grade, int passes);
+// Whether the dispatch rule gives it the cascade: the measured range, a total halo of at most
+// 2 KiB, 256 B for two int16 passes (mavg_cascade.hip).
+bool cascade_tile_preferred(int dtype, int C, int grade, int passes);
+// MAVG_ERR_UNSUPPORTED: the cascade does not fit, or the launch would exceed grid_too_large
+int cascade_tile_any(int dtype, int C, const CascadeSig& cs, int grade, int passes, hipStream_t st);
+
 // ceil(k / F): the units a k-frame halo takes (TileParams / AheadParams halo_units)
 template <int F>
 constexpr size_t tile_halo_units(int k) { return (size_t)(((long long)k + F - 1) / F); }

@@ -347,6 +347,87 @@ int mavg_decim_workspace_bytes(size_t n_samples, int channels, int grade, int ho
 int mavg_decim_plan(size_t n_samples, int channels, int grade, int hop, int phase, int dtype,
                     char* buf, size_t buflen);
 
+/*
+ * Cascaded moving average: `passes` >= 1 boxcar passes of one window `grade`,
+ * exactly what `passes` successive mavg_run calls with zero history produce,
+ * the intermediate stored in the signal's own dtype between passes: int16
+ * takes the exact sum, divides with truncation by grade and casts to int16 in
+ * every pass (bit-exact with the CPU oracle applied `passes` times); fp32
+ * accumulates in fp64, computes float(S / grade), and the intermediate is
+ * rounded to fp32.  The divisor is grade in the warm-up of every pass.  Two
+ * passes give a triangular window, three or four the usual Gaussian
+ * approximation.
+ *   d_history  NULL: frames before frame 0 read as zero in every pass (the same
+ *              as passes * (grade-1) zero frames in front of the signal).  Else
+ *              the passes * (grade-1) * channels samples that immediately
+ *              precede d_in: the outputs are those of the cascade applied to
+ *              concat(history, x) with the first passes * (grade-1) frames
+ *              dropped -- exact for int16 too, every intermediate sample depends
+ *              on a finite window: what a chunked streaming caller needs.
+ *   d_in, d_out  any sample-aligned views of n_samples samples that do not
+ *              overlap; views that are not both 16-B aligned run the fused
+ *              kernel's one-frame-per-lane form (no head is peeled).
+ *   d_ws       mavg_cascade_workspace_bytes() bytes, 16-B aligned (NULL when 0).
+ * Ownership, stream and capture rules are mavg_run's: no allocation, no
+ * synchronisation, every step planned before the first is launched, nothing
+ * enqueued unless MAVG_OK is returned (MAVG_ERR_HIP excepted).  n_samples == 0:
+ * MAVG_OK, nothing enqueued.  Nothing new is promised for non-finite fp32
+ * inputs.
+ *
+ * Status: MAVG_ERR_INVALID_ARG for passes < 1 and mavg_run's invalid cases;
+ * MAVG_ERR_UNSUPPORTED when passes * (grade-1) does not fit an int;
+ * MAVG_ERR_MISALIGNED, MAVG_ERR_WORKSPACE and MAVG_ERR_UNSUPPORTED as mavg_run.
+ *
+ * Dispatch, evaluated in this order (mavg_cascade_plan shows which):
+ *   cascade_none  passes == 1 or grade == 1 (every pass a copy): mavg_run
+ *                 (MAVG_ALGO_AUTO, block_size 0), unchanged, with its workspace.
+ *   cascade_tile  ONE launch, no workspace: channels 1 or 2, grade >= 2 (int16:
+ *                 <= 65535), a total halo passes * (grade-1) * channels * sample
+ *                 size of at most 2 KiB -- 256 B for two int16 passes -- (the
+ *                 measured range, DESIGN.md "Cascade": at 8 KiB it measured
+ *                 slower than the loop; the kernel itself takes up to 16 KiB
+ *                 and an LDS layout inside the workgroup's budget in both unit
+ *                 forms, which mavg_debug_force_cascade can force).  A tile
+ *                 stages its frames and the total halo in LDS and runs every
+ *                 pass there: the signal is read once (plus the halo, mostly
+ *                 from L2) and written once, whatever `passes`.
+ *   cascade_loop  everything else: mavg_run (AUTO, block_size 0) `passes` times
+ *                 on `stream`, never in place, alternating between d_out and a
+ *                 workspace buffer so that the last pass lands in d_out --
+ *                 correct, not fast.  With a history, pass j also filters the
+ *                 shrinking history block ((passes-j+1) * (grade-1) frames, zero
+ *                 history, the first grade-1 outputs dropped) into the history
+ *                 of pass j+1, and itself takes the block's last grade-1 frames.
+ *                 Workspace, with s the sample size and r16 rounding up to 16:
+ *                   r16(n_samples * s)
+ *                   + (history ? 2 * r16(passes * (grade-1) * channels * s) : 0)
+ *                   + max(mavg_workspace_bytes(n_samples),
+ *                         history ? mavg_workspace_bytes(passes * (grade-1) * channels) : 0)
+ *                 (both mavg_workspace_bytes at MAVG_ALGO_AUTO, block_size 0).
+ *
+ * Supported maximum.  mavg_run's: cascade_tile makes one launch of `block`
+ * threads per `tile_frames` frames (both in mavg_cascade_plan's text), past it
+ * MAVG_ERR_UNSUPPORTED and nothing is enqueued.  NOT tested past 2^31 samples
+ * (frame and sample indices that are not tile-local are 64-bit in the kernel).
+ */
+int mavg_cascade_run(const void* d_in, void* d_out, size_t n_samples, int channels, int grade,
+                     int passes, int dtype, const void* d_history,
+                     void* d_ws, size_t ws_bytes, void* stream);
+
+/* Device workspace (bytes) mavg_cascade_run needs: mavg_workspace_bytes for
+ * cascade_none, 0 for cascade_tile, the formula above for cascade_loop
+ * (with_history != 0: a d_history will be passed). */
+int mavg_cascade_workspace_bytes(size_t n_samples, int channels, int grade, int passes, int dtype,
+                                 int with_history, size_t* out_bytes);
+
+/* Describe, without launching anything, what mavg_cascade_run would do on
+ * 16-B-aligned views: "cascade_none x <mavg_plan's text>", "cascade_tile<...>
+ * ... passes=P halo_frames=H ... tile_frames=N ..." or "cascade_loop passes=P
+ * history=0|1 x <mavg_plan's text>" (up to ~300 characters).  n_samples == 0
+ * has no plan: MAVG_ERR_INVALID_ARG. */
+int mavg_cascade_plan(size_t n_samples, int channels, int grade, int passes, int dtype,
+                      int with_history, char* buf, size_t buflen);
+
 /* Describe, without launching anything, the kernel and launch geometry
  * mavg_run would use for these arguments on 16-B-aligned views
  * (e.g. "tile_scan<f32,...> grid=... block=256 ..."). */

@@ -37,6 +37,18 @@ int mavg_test_ahead_schedule(int slots, int spin);
  * MAVG_ERR_INVALID_ARG for another value (nothing changes). */
 int mavg_debug_force_decim(int path);
 
+/* TEST HOOK (parity tests and tools/bench_cascade.py): force mavg_cascade_run's
+ * path for passes >= 2 and grade >= 2 -- 0: the dispatch rule decides (the
+ * default), 1: cascade_tile, 2: cascade_loop -- so that both paths can run on
+ * one shape.  A forced cascade_tile runs wherever the kernel can take the
+ * shape (up to 16 KiB of total halo, not only the rule's measured range); one
+ * that cannot take the shape makes
+ * mavg_cascade_run, mavg_cascade_plan and mavg_cascade_workspace_bytes return
+ * MAVG_ERR_UNSUPPORTED; cascade_none stays.  Process-wide, like the schedule
+ * hook; returns MAVG_OK, or MAVG_ERR_INVALID_ARG for another value (nothing
+ * changes). */
+int mavg_debug_force_cascade(int path);
+
 #ifdef __cplusplus
 }
 #endif
