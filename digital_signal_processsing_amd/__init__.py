@@ -10,6 +10,7 @@ only for device memory and streams.
     y = moving_average_rows(x, grade=1024)             # [B, T] / [C, T] / [B, C, T]: every row on its own
     y = moving_average_ragged(x, grade=1024, lengths=[5, 0, 30011, 7])   # packed rows of different lengths
     y = moving_average_decimated(x, grade=400, hop=160)  # only every hop-th output frame, in one launch
+    y = moving_rms(x, grade=1024)                      # fp32 RMS / variance / std of the window, one launch
 
 Semantics: ``basics/profilable_moving_averager.cpp:14-37`` -- interleaved
 frames, window ``grade`` frames, zero history (or ``history``: the
@@ -21,7 +22,7 @@ from __future__ import annotations
 from typing import Optional
 
 from . import _lib
-from ._lib import (ALGOS, F32, I16, MavgError, MavgLibraryError, algo_name,  # noqa: F401
+from ._lib import (ALGOS, F32, I16, STATS, MavgError, MavgLibraryError, algo_name,  # noqa: F401
                    strerror)
 
 __all__ = [
@@ -44,6 +45,14 @@ __all__ = [
     "moving_average_cascade_into",
     "cascade_plan",
     "cascade_workspace_bytes",
+    "moving_stat",
+    "moving_stat_into",
+    "moving_rms",
+    "moving_variance",
+    "moving_std",
+    "moving_mean_square",
+    "stat_plan",
+    "STATS",
     "fill_synthetic",
     "workspace_bytes",
     "resolve_algo",
@@ -622,6 +631,104 @@ def moving_average_cascade(x, grade: int, passes: int, channels: int = 1, histor
     C = channels if x.dim() == 1 else x.shape[1]
     return _with_out(x, stream, lambda out: moving_average_cascade_into(x, out, grade, passes, C, history, stream,
                                                                         library=library), (x, history))
+
+
+def _stat_code(stat) -> int:
+    if isinstance(stat, bool):
+        raise ValueError(f"unknown stat {stat!r}; one of {sorted(STATS)} or 0..3")
+    if isinstance(stat, int):
+        if stat not in STATS.values():
+            raise ValueError(f"unknown stat {stat!r}; one of {sorted(STATS)} or 0..3")
+        return stat
+    try:
+        return STATS[stat]
+    except (KeyError, TypeError):
+        raise ValueError(f"unknown stat {stat!r}; one of {sorted(STATS)} or 0..3") from None
+
+
+def stat_plan(n: int, grade: int, stat, channels: int = 1, dtype: int = F32, with_mean: bool = False,
+              library: Optional[str] = None) -> str:
+    """What mavg_stat_run would do (nothing is launched): ``stat_tile<...> ... tile_frames=N ...``
+    or ``stat_strip ... L=...``."""
+    import ctypes
+    buf = ctypes.create_string_buffer(512)
+    _lib.check(_lib.load(library).mavg_stat_plan(n, channels, grade, _stat_code(stat), dtype, int(bool(with_mean)), buf,
+                                                 len(buf)), "mavg_stat_plan")
+    return buf.value.decode()
+
+
+def moving_stat_into(x, out, grade: int, stat, channels: int = 1, history=None, mean_out=None, stream=None,
+                     library: Optional[str] = None) -> None:
+    """Enqueue ``out = moving_stat(x)`` on ``stream`` (default: current), one launch, no workspace.
+
+    ``out`` (and ``mean_out``, which receives the window mean): contiguous ``float32`` device
+    tensors of ``x``'s size that do not overlap ``x``.  ``history``: the ``(grade-1) * channels``
+    samples in front of ``x``."""
+    torch = _torch()
+    code = _stat_code(stat)
+    frames, C = _decim_shape(x, channels)
+    dt = _dtype_code(x)
+    for t, what in ((out, "out"), (mean_out, "mean_out")):
+        if t is None:
+            continue
+        if t.dtype != torch.float32:
+            raise ValueError(f"{what} must be float32 (the statistics are fp32 for every input dtype), got {t.dtype}")
+        if t.numel() != x.numel():
+            raise ValueError(f"{what} must hold x's {x.numel()} samples, got {t.numel()}")
+    _check_device_pair(x, out)
+    if mean_out is not None:
+        _check_device_pair(x, mean_out)
+    hist_ptr = _history_ptr(history, x, (grade - 1) * C, "(grade-1)*channels")
+    st = _lib.load(library).mavg_stat_run(x.data_ptr(), out.data_ptr(),
+                                          mean_out.data_ptr() if mean_out is not None else None, x.numel(), C, grade,
+                                          code, dt, hist_ptr, _stream_handle(stream, x.device))
+    _lib.check(st, "mavg_stat_run")
+
+
+def moving_stat(x, grade: int, stat, channels: int = 1, history=None, with_mean: bool = False, stream=None,
+                library: Optional[str] = None):
+    """A statistic of the causal ``grade``-frame window of ``x`` (fp32 or int16), per channel, as
+    ``float32`` in ``x``'s shape: ``stat`` = ``"meansq"`` (S2/k), ``"rms"``, ``"var"`` (population
+    variance, clamped at 0) or ``"std"`` -- or the ``mavg_stat`` value.  The divisor is ``grade``
+    everywhere (the warm-up sees a zero-padded window, or ``history``).  ``with_mean``: return
+    ``(y, mean)``, the window mean from the same launch.  fp32 variance is accurate to 1e-5 of the
+    window's mean SQUARE: remove a large DC offset first."""
+    torch = _torch()
+    _check_device_x(x)
+    _stat_code(stat)
+    _decim_shape(x, channels)
+    _dtype_code(x)
+    C = channels if x.dim() == 1 else x.shape[1]
+    like = x.new_empty(0, dtype=torch.float32)  # _with_out's model: x's device, float32
+    mean = []
+
+    def into(out):
+        if with_mean:
+            mean.append(_on_stream(stream, lambda: torch.empty_like(out)))
+        moving_stat_into(x, out, grade, stat, C, history, mean[0] if mean else None, stream, library)
+
+    out = _with_out(like, stream, into, (x, history), tuple(x.shape))
+    return (out, mean[0]) if with_mean else out
+
+
+def moving_mean_square(x, grade: int, channels: int = 1, **kw):
+    """``moving_stat(x, grade, "meansq", ...)``: the window's mean square S2/k."""
+    return moving_stat(x, grade, "meansq", channels, **kw)
+
+
+def moving_rms(x, grade: int, channels: int = 1, **kw):
+    """``moving_stat(x, grade, "rms", ...)``: the window's root mean square."""
+    return moving_stat(x, grade, "rms", channels, **kw)
+
+
+def moving_variance(x, grade: int, channels: int = 1, **kw):
+    """``moving_stat(x, grade, "var", ...)``: the window's population variance."""
+    return moving_stat(x, grade, "var", channels, **kw)
+
+
+def moving_std(x, grade: int, channels: int = 1, **kw):
+    """``moving_stat(x, grade, "std", ...)``: the window's population standard deviation."""
+    return moving_stat(x, grade, "std", channels, **kw)
 
 
 def fill_synthetic(n: int, dtype=None, seed: int = 0x5EED, offset: int = 0, dist: int = 0,

@@ -499,6 +499,45 @@ int cascade_tile_launch(const CascadeCall& a, hipStream_t s) {
   return cascade_tile_any(a.dtype, a.C, cs, a.k, a.passes, s);
 }
 
+// ---- moments (mavg_stat_run) -----------------------------------------------------------------
+int validate_stat(size_t n, int C, int k, int stat, int dtype) {
+  if (stat < MAVG_STAT_MEANSQ || stat > MAVG_STAT_STD) return MAVG_ERR_INVALID_ARG;
+  return validate(n, C, k, dtype, MAVG_ALGO_AUTO, 0);
+}
+
+// The dispatch rule, in the order mavg.h gives; *path = kStatTile / kStatStrip: the tile kernel
+// wherever it takes the window (stat_tile_fits; it measured faster than the strip over that whole range).  The test hook's
+// forced path replaces the rule: MAVG_ERR_UNSUPPORTED where the tile kernel cannot take the shape.
+int stat_path(int C, int k, int dtype, int* path) {
+  const bool tile_ok = stat_tile_fits(dtype, C, k);
+  int forced = kStatAuto;
+#ifdef MAVG_TEST_HOOKS
+  forced = g_test_stat_path.load(std::memory_order_relaxed);
+#endif
+  if (forced == kStatTile && !tile_ok) return MAVG_ERR_UNSUPPORTED;
+  *path = forced != kStatAuto ? forced : tile_ok ? kStatTile : kStatStrip;
+  return MAVG_OK;
+}
+
+struct StatCall {
+  const void* in;
+  float* out;
+  float* mean;
+  const void* hist;
+  size_t n;
+  int C, k, stat, dtype;
+};
+
+// The one launch of stat_tile / stat_strip (plan mode when g_plan is set); views of any sample
+// alignment.
+int stat_launch(int path, const StatCall& a, hipStream_t s) {
+  StatSig ss{a.in, a.out, a.mean, a.hist, a.n / (size_t)a.C};
+  if (path == kStatStrip) return stat_strip_any(a.dtype, a.C, ss, a.k, a.stat, s);
+  ss.unit = aligned(a.in, 16) && aligned(a.out, 16) && (a.mean == nullptr || aligned(a.mean, 16));
+  ss.eio = !ss.unit && !aligned(a.in, elem_size(a.dtype) * (size_t)a.C) ? 1 : 0;
+  return stat_tile_any(a.dtype, a.C, ss, a.k, a.stat, s);
+}
+
 // cascade_loop's workspace, in this order: the ping-pong buffer (the signal's bytes, 16-B padded);
 // with a history two block buffers of passes * (grade - 1) * C samples each (16-B padded); then
 // mavg_run's own workspace -- the signal's, and with a history at least the first block's.
@@ -896,6 +935,42 @@ int mavg_cascade_run(const void* d_in, void* d_out, size_t n_samples, int channe
   const CascadeCall a{d_in, d_out, d_history, n_samples, channels, grade, passes, dtype};
   if (path == kCascadeTile) return cascade_tile_launch(a, static_cast<hipStream_t>(stream));
   return cascade_loop_run(a, d_ws, ws_bytes, stream);
+}
+
+int mavg_stat_plan(size_t n_samples, int channels, int grade, int stat, int dtype, int with_mean, char* buf,
+                   size_t buflen) {
+  if (buf == nullptr || buflen == 0) return MAVG_ERR_INVALID_ARG;
+  buf[0] = 0;
+  int st = validate_stat(n_samples, channels, grade, stat, dtype);
+  if (st != MAVG_OK) return st;
+  if (n_samples == 0) return MAVG_ERR_INVALID_ARG;  // nothing to describe, as mavg_plan
+  int path = kStatStrip;
+  st = stat_path(channels, grade, dtype, &path);
+  if (st != MAVG_OK) return st;
+  PlanScope ps;
+  float* const mean = with_mean != 0 ? static_cast<float*>(const_cast<void*>(kPlanOff)) : nullptr;
+  st = stat_launch(path, StatCall{kPlanIn, static_cast<float*>(kPlanOut), mean, nullptr, n_samples, channels, grade, stat, dtype},
+                   nullptr);
+  if (st == MAVG_OK) snprintf(buf, buflen, "%s", ps.plan.text);
+  return st;
+}
+
+// One launch: the tile kernel where the rule (stat_path) takes the window, else the strip kernel.
+int mavg_stat_run(const void* d_in, float* d_out, float* d_mean, size_t n_samples, int channels, int grade, int stat,
+                  int dtype, const void* d_history, void* stream) {
+  int st = validate_stat(n_samples, channels, grade, stat, dtype);
+  if (st != MAVG_OK) return st;
+  if (n_samples == 0) return MAVG_OK;
+  if (d_in == nullptr || d_out == nullptr) return MAVG_ERR_INVALID_ARG;
+  const size_t eb = elem_size(dtype);
+  if (!aligned(d_in, eb) || !aligned(d_out, 4) || (d_mean != nullptr && !aligned(d_mean, 4)) ||
+      (d_history != nullptr && !aligned(d_history, eb)))
+    return MAVG_ERR_MISALIGNED;
+  int path = kStatStrip;
+  st = stat_path(channels, grade, dtype, &path);
+  if (st != MAVG_OK) return st;
+  return stat_launch(path, StatCall{d_in, d_out, d_mean, d_history, n_samples, channels, grade, stat, dtype},
+                     static_cast<hipStream_t>(stream));
 }
 
 int mavg_ragged_workspace_bytes(const int64_t* h_offsets, size_t rows, int channels, int grade, int dtype,

@@ -10,6 +10,7 @@ std::atomic<int> g_test_ahead_slots{-1};
 std::atomic<int> g_test_ahead_spin{-1};
 std::atomic<int> g_test_decim_path{kDecimAuto};
 std::atomic<int> g_test_cascade_path{kCascadeAuto};
+std::atomic<int> g_test_stat_path{kStatAuto};
 #endif
 
 // ---- per-device attribute cache (no stream work, capture-safe) --------------
@@ -58,6 +59,11 @@ extern "C" int mavg_debug_force_decim(int path) {
 extern "C" int mavg_debug_force_cascade(int path) {
   if (path < mavg::kCascadeAuto || path > mavg::kCascadeLoop) return MAVG_ERR_INVALID_ARG;
   mavg::g_test_cascade_path.store(path, std::memory_order_relaxed);
+  return MAVG_OK;
+}
+extern "C" int mavg_debug_force_stat(int path) {
+  if (path < mavg::kStatAuto || path > mavg::kStatStrip) return MAVG_ERR_INVALID_ARG;
+  mavg::g_test_stat_path.store(path, std::memory_order_relaxed);
   return MAVG_OK;
 }
 #endif

@@ -249,6 +249,36 @@ bool cascade_tile_preferred(int dtype, int C, int grade, int passes);
 // MAVG_ERR_UNSUPPORTED: the cascade does not fit, or the launch would exceed grid_too_large
 int cascade_tile_any(int dtype, int C, const CascadeSig& cs, int grade, int passes, hipStream_t st);
 
+// The moving second moment (mavg_stat.hpp, instantiated in mavg_stat.hip): mean square, RMS,
+// variance or standard deviation (stat: mavg_stat) of the grade-frame window, fp32 out, one launch;
+// hist holds grade - 1 frames or is NULL; mean receives the window mean or is NULL.
+//   unit  the 16-B-unit form (in, out and mean all 16-B aligned); else the frame-unit (F = 1) form
+//   eio   frame-unit form on an input that is only element-aligned (UnitIO::gload)
+struct StatSig {
+  const void* in;
+  float* out;
+  float* mean;
+  const void* hist;
+  size_t nframes;
+  bool unit = true;
+  int eio = 0;
+};
+// The test hook's forced path (mavg_debug_force_stat, include/mavg_debug.h): 0 = the rule decides
+constexpr int kStatAuto = 0, kStatTile = 1, kStatStrip = 2;
+#ifdef MAVG_TEST_HOOKS
+extern std::atomic<int> g_test_stat_path;
+#endif
+// Whether the tile kernel takes this window (the dispatch rule, and what a forced stat_tile may
+// run): channels 1 or 2, grade >= 2, int16 grade <= 65535, a halo grade * C * sample size of at
+// most 16 KiB, and its LDS layout (StatLds) inside lds_budget in both forms.
+bool stat_tile_fits(int dtype, int C, int grade);
+// MAVG_ERR_UNSUPPORTED: the window does not fit, or the launch would exceed grid_too_large
+int stat_tile_any(int dtype, int C, const StatSig& ss, int grade, int stat, hipStream_t st);
+// The strip kernel: every channels, grade and sample-aligned view; L = stat_strip_frames(grade)
+// frames per thread.  MAVG_ERR_UNSUPPORTED: the launch would exceed grid_too_large.
+int stat_strip_frames(int grade);
+int stat_strip_any(int dtype, int C, const StatSig& ss, int grade, int stat, hipStream_t st);
+
 // ceil(k / F): the units a k-frame halo takes (TileParams / AheadParams halo_units)
 template <int F>
 constexpr size_t tile_halo_units(int k) { return (size_t)(((long long)k + F - 1) / F); }

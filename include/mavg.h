@@ -428,6 +428,96 @@ int mavg_cascade_workspace_bytes(size_t n_samples, int channels, int grade, int 
 int mavg_cascade_plan(size_t n_samples, int channels, int grade, int passes, int dtype,
                       int with_history, char* buf, size_t buflen);
 
+/* Moving second moment: mean square, RMS, population variance or standard
+ * deviation of the causal grade-frame window, per channel, in ONE launch.  With
+ * k = grade, S1 = sum of x and S2 = sum of x^2 over the k frames ending at
+ * frame f:
+ *   MAVG_STAT_MEANSQ  S2 / k
+ *   MAVG_STAT_RMS     sqrt(S2 / k)
+ *   MAVG_STAT_VAR     max(0, (k S2 - S1^2) / k^2)      (population variance)
+ *   MAVG_STAT_STD     sqrt(VAR)
+ * Frames before frame 0 read as zero, or as d_history (the (grade-1) * channels
+ * samples in front of d_in, exactly as in mavg_run); the divisor is `grade`
+ * everywhere, so the warm-up outputs are the statistics of the zero-padded
+ * window.  The output is ALWAYS fp32, for int16 input too (n_samples floats, in
+ * d_in's layout).  d_mean (fp32, n_samples floats, or NULL) receives
+ * (float)(S1 / k) from the same launch -- for z-scoring.
+ *
+ * int16 input: S1 and S2 are exact integers.  For grade <= 65535,
+ * N = k S2 - S1^2 is formed exactly in int64 and the output is the fp32
+ * rounding of an fp64 evaluation of N / k^2 (a reciprocal multiply) or its
+ * square root: a window of equal samples gives VAR and STD of exactly 0.0f, and
+ * outputs do not depend on how a signal is tiled or chunked.  For grade > 65535
+ * the result is formed in fp64 from the exact S1 and S2 and carries the fp32
+ * tolerance below.
+ * fp32 input: S1 and S2 accumulate in fp64 (x^2 is exact there).  MEANSQ and
+ * RMS are accurate to 1e-5 relative.  VAR is accurate to 1e-5 of the window's
+ * mean SQUARE, not of itself: S2/k - (S1/k)^2 cancels.  Windows of at most 16
+ * frames are summed directly, sample by sample, and hold these bars whatever
+ * precedes them; longer windows are running sums (prefix differences in fp64,
+ * as in mavg_run) with an absolute error near 1e-15 of the largest window sum
+ * of squares nearby (the same tile, a few thousand frames), so the bars hold
+ * while the window's mean square stays above about 1e-10 of that -- a signal
+ * that falls silent by more than 100 dB keeps a residue of that size.  A signal with a large
+ * DC offset loses that much of its variance; remove the offset first (subtract
+ * a constant, or this library's moving mean) when the variance is small beside
+ * the squared mean.  The clamp at 0 is part of the contract: STD is never NaN
+ * for finite input.  Nothing new is promised for non-finite input.
+ *
+ *   d_in       n_samples samples of `dtype`, sample-aligned.
+ *   d_out      n_samples floats, 4-B aligned; must not overlap d_in.
+ *   d_mean     n_samples floats, 4-B aligned, or NULL.
+ *   d_history  (grade-1) * channels samples or NULL, sample-aligned.
+ * The 16-B-unit form of the tile kernel runs when d_in, d_out and d_mean are
+ * all 16-B aligned; other views run its frame-unit form.  No workspace.
+ * Ownership, stream and capture rules are mavg_run's: no allocation, no
+ * synchronisation, nothing enqueued unless MAVG_OK is returned (MAVG_ERR_HIP
+ * excepted).  n_samples == 0: MAVG_OK, nothing enqueued.
+ *
+ * Status: MAVG_ERR_INVALID_ARG for a bad stat or dtype, channels < 1,
+ * grade < 1, n_samples not a multiple of channels, or a NULL d_in or d_out with
+ * work to do; MAVG_ERR_MISALIGNED for d_in (or d_history) off sample alignment
+ * or d_out or d_mean off 4 B; MAVG_ERR_UNSUPPORTED past the one-launch limit
+ * below.
+ *
+ * Dispatch, evaluated in this order (mavg_stat_plan shows which):
+ *   stat_tile   channels 1 or 2, grade >= 2 (int16: <= 65535), a halo grade *
+ *               channels * sample size of at most 16 KiB (the tile scan's and
+ *               the rows scan's limit; measured 4.7x and more faster than the
+ *               strip over that whole range, DESIGN.md "Moments").  A tile stages its frames and the halo in
+ *               LDS once and scans x[n]^2 - x[n-k]^2 from the stage; S1 is
+ *               scanned beside it only for VAR, STD or a d_mean.  About
+ *               8 B/sample of traffic for fp32, 6 for int16 (plus 4 per d_mean).
+ *   stat_strip  everything else (grade == 1, three or more channels, longer
+ *               halos, int16 grade > 65535): one thread per channel of a strip
+ *               of L frames (L = clamp(grade / 4, 16, 2048), in the plan text)
+ *               sums the window in front of its strip directly and slides it --
+ *               correct, not fast (about grade / L + 2 reads per output).
+ *
+ * Supported maximum.  One launch of at most 2^32 - 1 work-items: stat_tile runs
+ * `block` threads per `tile_frames` frames (both in the plan text; the frame-unit
+ * form, 4 frames per thread, refuses from 2^34 frames), stat_strip one thread
+ * per L frames and channel; past it MAVG_ERR_UNSUPPORTED and nothing is
+ * enqueued.  NOT tested past 2^31 samples (frame and sample indices that are
+ * not tile-local are 64-bit in the kernels).
+ */
+typedef enum {
+  MAVG_STAT_MEANSQ = 0,
+  MAVG_STAT_RMS = 1,
+  MAVG_STAT_VAR = 2,
+  MAVG_STAT_STD = 3
+} mavg_stat;
+int mavg_stat_run(const void* d_in, float* d_out, float* d_mean /* or NULL */, size_t n_samples,
+                  int channels, int grade, int stat, int dtype, const void* d_history,
+                  void* stream);
+
+/* Describe, without launching anything, what mavg_stat_run would do on
+ * 16-B-aligned views: "stat_tile<...> stat=S mean=0|1 ... tile_frames=N ..." or
+ * "stat_strip dtype=... L=... strips=...".  with_mean != 0: a d_mean will be
+ * passed.  n_samples == 0 has no plan: MAVG_ERR_INVALID_ARG. */
+int mavg_stat_plan(size_t n_samples, int channels, int grade, int stat, int dtype,
+                   int with_mean, char* buf, size_t buflen);
+
 /* Describe, without launching anything, the kernel and launch geometry
  * mavg_run would use for these arguments on 16-B-aligned views
  * (e.g. "tile_scan<f32,...> grid=... block=256 ..."). */

@@ -49,6 +49,16 @@ int mavg_debug_force_decim(int path);
  * changes). */
 int mavg_debug_force_cascade(int path);
 
+/* TEST HOOK (parity tests and tools/bench_stat.py): force mavg_stat_run's path
+ * -- 0: the dispatch rule decides (the default), 1: stat_tile, 2: stat_strip --
+ * so that both paths can run on one shape.  A forced stat_tile that cannot take
+ * the shape (three or more channels, grade == 1, a halo past 16 KiB, int16
+ * grade > 65535) makes mavg_stat_run and mavg_stat_plan return
+ * MAVG_ERR_UNSUPPORTED; the strip takes every shape.  Process-wide, like the
+ * schedule hook; returns MAVG_OK, or MAVG_ERR_INVALID_ARG for another value
+ * (nothing changes). */
+int mavg_debug_force_stat(int path);
+
 #ifdef __cplusplus
 }
 #endif

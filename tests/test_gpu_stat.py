@@ -1,0 +1,322 @@
+"""GPU tests of the moving second moment (moving_stat -> mavg_stat_run): the tile kernel
+(stat_tile, csrc/mavg_stat.hpp) and the strip kernel (stat_strip), by the rule and forced through
+the hooks build.
+
+The reference is tests/stat_ref.py, a numpy restatement of the definitions of include/mavg.h.
+Pass criteria (stat_ref.check_i16 / check_f32):
+  int16 input  |y - ref| <= one fp32 ulp at ref, exactly 0.0f where ref == 0 (y and ref are fp32
+               roundings of fp64 values that agree to a few 2^-52: a derived bound); the two
+               kernels agree bitwise.  grade > 65535 (fp64 moments): the fp32 bars.
+  fp32 input   with M the window's mean square in float64: MEANSQ and RMS 1e-5 relative; VAR
+               |y - ref| <= 1e-5 M; STD |y^2 - ref^2| <= 1e-5 M + 2^-22 ref^2, finite, >= 0;
+               d_mean against oracle.mavg_f32 within 1e-5 max(|ref|, window mean of |x|).
+Every case asserts the plan token, checks every output and the guard regions around d_out and
+d_mean.  Signals are three tiles plus 17 frames (tile_frames from the plan) unless stated; a signal
+and its window sums are computed once per (kind, C, frames, k, history) and shared."""
+import os
+import re
+
+import numpy as np
+import pytest
+
+import stat_ref
+from stat_ref import MEANSQ, RMS, STD, VAR
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HOOKS_LIB = os.path.join(ROOT, "digital_signal_processsing_amd", "lib", "libmavg_hooks.so")
+
+TILE, STRIP = "stat_tile<", "stat_strip "
+KINDS = [("i16", 1), ("i16", 2), ("f32d0", 1), ("f32d2", 1), ("f32d2", 2)]
+ALL_STATS = (MEANSQ, RMS, VAR, STD)
+GUARD = 7.0
+
+
+def _dsp():
+    import digital_signal_processsing_amd as dsp
+    return dsp
+
+
+def _dt(kind):
+    dsp = _dsp()
+    return dsp.I16 if kind == "i16" else dsp.F32
+
+
+def rule_boundary(kind, C):
+    """The largest grade the tile rule takes: a halo grade * C * sample size of 16 KiB."""
+    return 16384 // (C * (2 if kind == "i16" else 4))
+
+
+class Case:
+    """A signal, its history and what the references need, never modified."""
+
+    def __init__(self, oracle, kind, C, frames, k, with_hist, x=None):
+        self.kind, self.C, self.frames, self.k = kind, C, frames, k
+        pre = (k - 1) if with_hist else 0
+        if x is None:
+            seed = 7919 * frames + 31 * k + C + (5 if with_hist else 0)
+            n = (frames + pre) * C
+            long = oracle.synth_i16(n, seed=seed) if kind == "i16" else \
+                oracle.synth_f32(n, seed=seed, dist=0 if kind == "f32d0" else 2)
+        else:
+            long = x
+        self.x = np.ascontiguousarray(long[pre * C:])
+        self.hist = np.ascontiguousarray(long[:pre * C]) if with_hist else None
+        self.x.setflags(write=False)
+        self._refs = {}
+        if kind == "i16":
+            self.mean_ref = None
+        else:
+            # the project's bar for a moving mean: the oracle, and the window mean of |x| as the scale
+            m = oracle.mavg_f32(long, k, C).reshape(-1, C)[pre:]
+            a = np.abs(long.astype(np.float64)).reshape(-1, C)
+            P = np.concatenate([np.zeros((k, C)), np.cumsum(a, axis=0)])
+            self.mean_ref = (m.astype(np.float64), ((P[k:] - P[:-k]) / k)[pre:])
+
+    def ref(self, stat):
+        if stat not in self._refs:
+            if self.kind == "i16":
+                self._refs[stat] = stat_ref.stat_ref_i16(self.x, self.k, stat, self.C, self.hist)
+            else:
+                self._refs[stat] = stat_ref.stat_ref_f32(self.x, self.k, stat, self.C, self.hist)
+        return self._refs[stat]
+
+    def check(self, stat, y, mean, what):
+        if self.kind == "i16" and self.k <= 65535:
+            ref, mref = self.ref(stat)
+            stat_ref.check_i16(y, ref, what)
+            if mean is not None:
+                stat_ref.check_i16(mean, mref, (what, "mean"))
+            return
+        if self.kind == "i16":      # fp64 moments from the exact sums: the fp32 bars
+            ref, mref = self.ref(stat)
+            _, S2 = stat_ref.window_sums(self.x, self.k, self.C, self.hist)
+            stat_ref.check_f32(stat, y, ref.astype(np.float64), S2.astype(np.float64) / self.k, what)
+            if mean is not None:
+                stat_ref.check_i16(mean, mref, (what, "mean"))
+            return
+        ref, _, M = self.ref(stat)
+        stat_ref.check_f32(stat, y, ref, M, what)
+        if mean is not None:
+            m, F = self.mean_ref
+            bad = ~(np.abs(mean.astype(np.float64) - m) <= 1e-5 * np.maximum(np.abs(m), F))
+            assert not bad.any(), (what, "mean", int(bad.sum()), tuple(np.argwhere(bad)[0]))
+
+
+_cases = {}
+
+
+def case_of(oracle, kind, C, frames, k, with_hist=False):
+    key = (kind, C, frames, k, with_hist)
+    if key not in _cases:
+        _cases[key] = Case(oracle, kind, C, frames, k, with_hist)
+    return _cases[key]
+
+
+def plan_of(kind, C, frames, k, stat, with_mean=False, library=None):
+    return _dsp().stat_plan(frames * C, k, stat, C, _dt(kind), with_mean, library)
+
+
+def tile_frames(plan):
+    return int(re.search(r" tile_frames=(\d+) ", plan).group(1))
+
+
+def three_tiles(kind, C, k):
+    plan = plan_of(kind, C, 1 << 16, k, VAR)
+    assert plan.startswith(TILE), plan
+    return 3 * tile_frames(plan) + 17
+
+
+def run(dev, case, stat, family, with_mean=False, off_in=0, off_out=0, off_mean=0, library=None, x=None, hist=None):
+    """One launch on the device through views `off_*` samples into larger buffers; every output is
+    checked against the reference (unless x is given: a chunk, checked by the caller) and nothing
+    outside the views may be written.  Returns (y, mean or None) as [frames, C]."""
+    import torch
+    dsp = _dsp()
+    kind, C, k = case.kind, case.C, case.k
+    check = x is None
+    if check:
+        x, hist = case.x, case.hist
+    n = x.size
+    plan = plan_of(kind, C, n // C, k, stat, with_mean, library)
+    assert plan.startswith(family), (family, plan)
+    xbuf = torch.zeros(n + 8, dtype=torch.int16 if kind == "i16" else torch.float32, device=dev)
+    xv = xbuf[off_in:off_in + n]
+    xv.copy_(torch.tensor(x))
+    assert xv.data_ptr() % 16 == (off_in * xbuf.element_size()) % 16
+    ybuf = torch.full((n + 8,), GUARD, dtype=torch.float32, device=dev)
+    mbuf = torch.full((n + 8,), GUARD, dtype=torch.float32, device=dev)
+    yv = ybuf[off_out:off_out + n]
+    mv = mbuf[off_mean:off_mean + n] if with_mean else None
+    ht = torch.tensor(hist).to(dev) if hist is not None else None
+    dsp.moving_stat_into(xv, yv, k, stat, C, history=ht, mean_out=mv, library=library)
+    yb, mb = ybuf.cpu().numpy(), mbuf.cpu().numpy()
+    what = (kind, C, n // C, k, stat, with_mean, hist is not None, off_in, off_out, off_mean, plan)
+    assert (yb[:off_out] == GUARD).all() and (yb[off_out + n:] == GUARD).all(), ("written outside d_out", what)
+    if with_mean:
+        assert (mb[:off_mean] == GUARD).all() and (mb[off_mean + n:] == GUARD).all(), ("written outside d_mean", what)
+    else:
+        assert (mb == GUARD).all(), ("d_mean written without a mean", what)
+    y = yb[off_out:off_out + n].reshape(-1, C).copy()
+    mean = mb[off_mean:off_mean + n].reshape(-1, C).copy() if with_mean else None
+    if check:
+        case.check(stat, y, mean, what)
+    return y, mean
+
+
+class forced:
+    """A path forced on the hooks build, the rule restored on the way out."""
+
+    def __init__(self, path):
+        self.path = path
+
+    def __enter__(self):
+        from digital_signal_processsing_amd import _lib
+        self.lib = _lib.load(HOOKS_LIB)
+        assert self.lib.mavg_debug_force_stat(self.path) == _lib.OK
+        return HOOKS_LIB
+
+    def __exit__(self, *exc):
+        self.lib.mavg_debug_force_stat(0)
+
+
+def forced_strip():
+    from digital_signal_processsing_amd import _lib
+    return forced(_lib.STAT_STRIP)
+
+
+# ---- parity: the tile kernel by the rule, the strip forced on the same shapes ----
+@pytest.mark.gpu
+@pytest.mark.parametrize("kind,C", KINDS)
+@pytest.mark.parametrize("stat", ALL_STATS)
+def test_parity_tile_and_forced_strip(gpu, oracle_mod, kind, C, stat):
+    for k in (2, 3, 7, 64, 1000, 1024, rule_boundary(kind, C)):
+        case = case_of(oracle_mod, kind, C, three_tiles(kind, C, k), k)
+        y, _ = run(gpu, case, stat, TILE)
+        ym, mean = run(gpu, case, stat, TILE, with_mean=True)
+        with forced_strip() as lib:
+            ys, means = run(gpu, case, stat, STRIP, with_mean=True, library=lib)
+        if kind == "i16":   # exact sums, one output function: bitwise, whatever the kernel and the moment set
+            assert np.array_equal(y, ym) and np.array_equal(y, ys) and np.array_equal(mean, means), (kind, C, k, stat)
+
+
+# ---- the strip by the rule ----
+@pytest.mark.gpu
+@pytest.mark.parametrize("kind,C,k", [
+    ("i16", 1, 1), ("i16", 2, 1), ("f32d2", 1, 1), ("f32d2", 2, 1),
+    ("i16", 3, 100), ("f32d2", 3, 100), ("i16", 8, 100), ("f32d2", 8, 100),
+    ("i16", 1, 44100), ("f32d2", 1, 44100), ("f32d0", 1, 44100),
+    ("i16", 1, 65536),
+])
+def test_strip_by_rule(gpu, oracle_mod, kind, C, k):
+    case = case_of(oracle_mod, kind, C, 2 * k + 17, k)
+    for stat in ALL_STATS:
+        run(gpu, case, stat, STRIP, with_mean=stat in (RMS, VAR))
+
+
+@pytest.mark.gpu
+def test_strip_full_scale_window_has_zero_variance(gpu, oracle_mod):
+    """int16 mono k = 65535 on all -32768: k S2 and S1^2 are both just below 2^62 and equal."""
+    k = 65535
+    x = np.full(2 * k + 17, -32768, dtype=np.int16)
+    case = Case(oracle_mod, "i16", 1, x.size, k, False, x=x)
+    for stat in (VAR, STD):
+        y, mean = run(gpu, case, stat, STRIP, with_mean=True)
+        assert (y[k - 1:] == 0).all() and (mean[k - 1:] == -32768).all()
+    y, _ = run(gpu, case, RMS, STRIP)
+    assert (y[k - 1:] == 32768).all()
+
+
+# ---- views: the 16-B-unit form needs every view 16-B aligned, the frame-unit form takes the rest ----
+@pytest.mark.gpu
+@pytest.mark.parametrize("kind,C", KINDS)
+@pytest.mark.parametrize("off_in,off_out,off_mean", [(1, 0, 0), (0, 1, 0), (0, 0, 3), (3, 1, 0), (1, 3, 1), (2, 0, 0), (0, 0, 0)])
+def test_views(gpu, oracle_mod, kind, C, off_in, off_out, off_mean):
+    for k in (5, 100):
+        case = case_of(oracle_mod, kind, C, three_tiles(kind, C, k), k)
+        run(gpu, case, STD, TILE, with_mean=True, off_in=off_in, off_out=off_out, off_mean=off_mean)
+        run(gpu, case, RMS, TILE, off_in=off_in, off_out=off_out)     # S2 alone
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("kind,C", [("i16", 2), ("f32d2", 1)])
+def test_views_on_the_strip(gpu, oracle_mod, kind, C):
+    case = case_of(oracle_mod, kind, C, three_tiles(kind, C, 100), 100)
+    with forced_strip() as lib:
+        run(gpu, case, VAR, STRIP, with_mean=True, off_in=1, off_out=3, off_mean=1, library=lib)
+
+
+# ---- history: a signal filtered whole against the same signal in three chunks ----
+@pytest.mark.gpu
+@pytest.mark.parametrize("kind,C", KINDS)
+@pytest.mark.parametrize("path", ("tile", "strip"))
+def test_history_makes_chunks_exact(gpu, oracle_mod, kind, C, path):
+    from digital_signal_processsing_amd import _lib
+    k = 100
+    frames = three_tiles(kind, C, k)
+    TF = (frames - 17) // 3
+    case = case_of(oracle_mod, kind, C, frames, k)
+    cuts = [0, TF + 5, 2 * TF - 3, frames]          # no boundary on a tile multiple
+    family = TILE if path == "tile" else STRIP
+    with forced(_lib.STAT_TILE if path == "tile" else _lib.STAT_STRIP) as lib:
+        for stat in (VAR, RMS):
+            whole, wmean = run(gpu, case, stat, family, with_mean=True, library=lib)
+            ys, ms = [], []
+            for a, b in zip(cuts[:-1], cuts[1:]):
+                assert b - a >= k - 1
+                hist = case.x[(a - (k - 1)) * C:a * C] if a else None
+                y, m = run(gpu, case, stat, family, with_mean=True, library=lib, x=case.x[a * C:b * C], hist=hist)
+                ys.append(y)
+                ms.append(m)
+            y, m = np.concatenate(ys), np.concatenate(ms)
+            if kind == "i16":
+                assert np.array_equal(y, whole) and np.array_equal(m, wmean), (kind, C, path, stat)
+            case.check(stat, y, m, ("chunked", kind, C, path, stat))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("kind,C", KINDS)
+def test_a_given_history_is_the_signal_in_front(gpu, oracle_mod, kind, C):
+    """With d_history the warm-up outputs are those of the longer signal (the reference includes it)."""
+    for k in (7, 300):
+        case = case_of(oracle_mod, kind, C, three_tiles(kind, C, k), k, with_hist=True)
+        run(gpu, case, STD, TILE, with_mean=True)
+        with forced_strip() as lib:
+            run(gpu, case, STD, STRIP, with_mean=True, library=lib)
+
+
+# ---- constants ----
+@pytest.mark.gpu
+@pytest.mark.parametrize("C", (1, 2))
+def test_int16_constant_has_exactly_zero_variance(gpu, oracle_mod, C):
+    for k in (64, 1000):
+        frames = three_tiles("i16", C, k)
+        x = np.full(frames * C, 12345, dtype=np.int16)
+        case = Case(oracle_mod, "i16", C, frames, k, False, x=x)
+        for stat in (VAR, STD):
+            y, mean = run(gpu, case, stat, TILE, with_mean=True)      # the warm-up: per the reference
+            assert (y[k - 1:] == 0).all() and (y[:k - 1] > 0).all() and (mean[k - 1:] == 12345).all()
+
+
+@pytest.mark.gpu
+def test_fp32_constant_variance_is_clamped(gpu, oracle_mod):
+    for k in (64, 1000):
+        frames = three_tiles("f32d0", 1, k)
+        x = np.full(frames, 1000.1, dtype=np.float32)
+        case = Case(oracle_mod, "f32d0", 1, frames, k, False, x=x)
+        var, _ = run(gpu, case, VAR, TILE)
+        std, _ = run(gpu, case, STD, TILE, with_mean=True)
+        assert (var >= 0).all() and np.isfinite(std).all() and (std >= 0).all()
+        assert (std[k - 1:] <= np.sqrt(1e-5) * 1000.1).all()
+
+
+# ---- short signals: frames < grade and frames < tile_frames ----
+@pytest.mark.gpu
+@pytest.mark.parametrize("kind,C", KINDS)
+@pytest.mark.parametrize("frames", (1, 5, 63))
+def test_short_signals(gpu, oracle_mod, kind, C, frames):
+    for k in (100, 3):
+        case = case_of(oracle_mod, kind, C, frames, k)
+        for stat in (STD, MEANSQ):
+            run(gpu, case, stat, TILE, with_mean=stat == STD)
+        case = case_of(oracle_mod, kind, C, frames, k, with_hist=True)
+        run(gpu, case, VAR, TILE, with_mean=True, off_out=1)
