@@ -65,8 +65,8 @@ __host__ __device__ inline int cascade_first_unit(int halo_units, int xk_units, 
 // pass writes the tile's frames to d_out instead.  Pass j scans units [cascade_first_unit(j),
 // stage end): the span later passes still need, not the whole stage.
 // int16 sums are int32 prefix differences mod 2^32 (a window sum is below 2^31 for k <= 65535);
-// fp32 sums are fp64.  Frame and sample indices are 64-bit wherever they are not tile-local; not
-// tested past 2^31 samples (include/mavg.h).
+// fp32 sums are fp64.  Frame and sample indices are 64-bit wherever they are not tile-local; tested
+// on 2^32 + 10^6-sample signals (tests/test_gpu_bigsignal.py).
 // ----------------------------------------------------------------------------
 template <typename T, typename A, int C, int F, int U, int WG = kWG, int NT = kNtSplit | kNtHalo | kNtStore, int DV = 0>
 __global__ __launch_bounds__(WG) void cascade_tile_kernel(CascadeParams p) {

@@ -91,8 +91,8 @@ struct DecimLds {
 // the kept frames are converted, into the LDS compaction buffer; after a third barrier the
 // workgroup stores out[m_lo*C .. (m_lo+cnt)*C) contiguously: 16-B stores on the aligned interior,
 // element stores at the two ends.  A tile that keeps no frame (hop > TF) returns before it loads.
-// Frame and sample indices are 64-bit wherever they are not tile-local; not tested past 2^31
-// samples (include/mavg.h).
+// Frame and sample indices are 64-bit wherever they are not tile-local; tested on 2^32 +
+// 10^6-sample signals (tests/test_gpu_bigsignal.py).
 // ----------------------------------------------------------------------------
 template <typename T, typename A, int C, int F, int U, int WG = kWG, int NT = kNtSplit | kNtHalo | kNtStore, int DV = 0>
 __global__ __launch_bounds__(WG) void decim_scan_kernel(DecimParams p) {

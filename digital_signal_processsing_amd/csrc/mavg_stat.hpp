@@ -133,8 +133,8 @@ struct StatLds {
 // cost.  The stat is a wave-uniform choice at the output (StatOut).  The output, and the mean, are
 // fp32: a 16-B unit of F frames leaves as VE floats (an int16 unit of 8 samples as two 16-B
 // stores); the frame-unit form (F == 1, any sample-aligned views) stores elements.
-// Frame and sample indices are 64-bit wherever they are not tile-local; not tested past 2^31
-// samples (include/mavg.h).
+// Frame and sample indices are 64-bit wherever they are not tile-local; tested on 2^32 +
+// 10^6-sample signals (tests/test_gpu_bigsignal.py).
 // ----------------------------------------------------------------------------
 template <typename T, int C, int F, int U, int M, bool RC, int WG = kWG, int NT = kNtSplit | kNtHalo | kNtStore>
 __global__ __launch_bounds__(WG) void stat_tile_kernel(StatParams p) {

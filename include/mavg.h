@@ -322,8 +322,9 @@ int mavg_ragged_plan(const int64_t* h_offsets, size_t rows, int channels, int gr
  * Supported maximum.  mavg_run's: every kernel makes one launch
  * (decim_scan: `block` threads per `tile_frames` frames, decim_window: one wave
  * per output frame), past it MAVG_ERR_UNSUPPORTED and nothing is enqueued.
- * NOT tested past 2^31 samples (frame and sample indices that are not
- * tile-local are 64-bit in the kernels).
+ * decim_scan (both unit forms, with and without a history), decim_window and
+ * decim_full are tested on 2^32 + 10^6-sample signals, every output
+ * (tests/test_gpu_bigsignal.py).
  */
 int mavg_decim_run(const void* d_in, void* d_out, size_t n_samples, int channels, int grade,
                    int hop, int phase, int dtype, const void* d_history,
@@ -407,8 +408,9 @@ int mavg_decim_plan(size_t n_samples, int channels, int grade, int hop, int phas
  *
  * Supported maximum.  mavg_run's: cascade_tile makes one launch of `block`
  * threads per `tile_frames` frames (both in mavg_cascade_plan's text), past it
- * MAVG_ERR_UNSUPPORTED and nothing is enqueued.  NOT tested past 2^31 samples
- * (frame and sample indices that are not tile-local are 64-bit in the kernel).
+ * MAVG_ERR_UNSUPPORTED and nothing is enqueued.  cascade_tile (both unit forms, with
+ * and without a history) and cascade_loop are tested on 2^32 + 10^6-sample
+ * signals, every output (tests/test_gpu_bigsignal.py).
  */
 int mavg_cascade_run(const void* d_in, void* d_out, size_t n_samples, int channels, int grade,
                      int passes, int dtype, const void* d_history,
@@ -498,8 +500,9 @@ int mavg_cascade_plan(size_t n_samples, int channels, int grade, int passes, int
  * `block` threads per `tile_frames` frames (both in the plan text; the frame-unit
  * form, 4 frames per thread, refuses from 2^34 frames), stat_strip one thread
  * per L frames and channel; past it MAVG_ERR_UNSUPPORTED and nothing is
- * enqueued.  NOT tested past 2^31 samples (frame and sample indices that are
- * not tile-local are 64-bit in the kernels).
+ * enqueued.  stat_tile (both unit forms, the direct sums, with and without a
+ * history or a d_mean) and stat_strip are tested on 2^32 + 10^6-sample signals,
+ * every output (tests/test_gpu_bigsignal.py).
  */
 typedef enum {
   MAVG_STAT_MEANSQ = 0,

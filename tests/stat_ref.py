@@ -112,3 +112,27 @@ def check_f32(stat, y, ref, M, what=""):
     if bad.any():
         i = tuple(np.argwhere(bad)[0])
         raise AssertionError(f"{what}: {int(bad.sum())} mismatches, first at {i}: got {y[i]!r}, want {ref[i]!r} (M {M[i]!r})")
+
+
+# ---- a signal that falls silent (the fp32 dynamic-range clauses of include/mavg.h) ----
+LOUD, QUIET = 1e15, 1e-4      # loud amplitudes 0.5 .. 1.5 LOUD (squares near 1e30); quiet: dist 2 times QUIET (about 1e-3 and below)
+
+
+def falls_silent(oracle, C, frames, loud_frames, seed=0):
+    """fp32 [frames * C]: the first loud_frames frames near +-1e15, the rest the mixed-scale (dist 2)
+    generator scaled to about 1e-3 -- a drop of 360 dB."""
+    rng = np.random.default_rng(seed)
+    x = oracle.synth_f32(frames * C, seed=77 + seed, dist=2).astype(np.float64) * QUIET
+    n = loud_frames * C
+    x[:n] = LOUD * rng.uniform(0.5, 1.5, n) * rng.choice((-1.0, 1.0), n)
+    x = x.astype(np.float32)
+    x.setflags(write=False)
+    return x
+
+
+def summation_bound(y, k, S2, sigma, nterms):
+    """The textbook bound on a window sum of squares formed from `nterms` fp64 terms whose absolute
+    values sum to `sigma`, read back from the MEANSQ output y = fl32(s2 / k):
+    |y k - S2| <= nterms 2^-53 sigma + 2^-24 y k.  Returns the violations."""
+    yk = y.astype(np.float64) * k
+    return ~(np.abs(yk - S2) <= nterms * 2.0 ** -53 * sigma + 2.0 ** -24 * yk)

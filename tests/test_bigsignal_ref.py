@@ -108,3 +108,227 @@ def test_rejects_what_it_cannot_check():
         chunked_mismatches(x + 0.5, x, 2, 1, 8)                # fp32 sums would not be exact
     with pytest.raises(TypeError):
         chunked_mismatches(x.double(), x.double(), 2, 1, 8)
+
+
+# ---- the siblings: decimated, cascaded, second moment ----
+from bigsignal_ref import chunked_cascade_mismatches, chunked_decim_mismatches, chunked_stat_mismatches  # noqa: E402
+
+import stat_ref  # noqa: E402
+
+FR2 = 5 * 4096
+CH2 = (4096, 1009)            # divides FR2 / does not, and shorter than the overlaps below
+FR3 = 5 * 1024                # the second moment (stat_ref walks fp32 samples as Python integers)
+CH3 = (1024, 253)
+DECIM = [(7, 2, 1), (1500, 160, 80), (100, 700, 699), (1, 3, 0), (1100, 1, 0)]     # k, hop, phase
+CASC = {"i16": [(33, 2), (100, 3), (600, 3), (5, 1)], "f32": [(64, 4), (2, 3), (1024, 2)]}   # k, passes
+
+
+@functools.lru_cache(maxsize=None)
+def _sig(oracle_mod, C, dt, frames):
+    n = frames * C
+    x = oracle_mod.synth_i16(n, seed=100 + C) if dt == "i16" else oracle_mod.synth_f32(n, seed=100 + C, dist=0)
+    x.setflags(write=False)
+    return x
+
+
+def _mavg(oracle_mod, x, k, C):
+    return oracle_mod.mavg_i16(x, k, C) if x.dtype == np.int16 else oracle_mod.mavg_f32(x, k, C)
+
+
+@functools.lru_cache(maxsize=None)
+def _decim_pair(oracle_mod, C, k, hop, phase, dt, ff):
+    x = _sig(oracle_mod, C, dt, FR2)
+    y = _mavg(oracle_mod, x, k, C).reshape(-1, C)[ff:][phase::hop].reshape(-1).copy()
+    return torch.from_numpy(x.copy()), torch.from_numpy(y)
+
+
+@functools.lru_cache(maxsize=None)
+def _cascade_pair(oracle_mod, C, k, passes, dt):
+    x = _sig(oracle_mod, C, dt, FR2)
+    y = x
+    for _ in range(passes):
+        y = _mavg(oracle_mod, y, k, C)
+    return torch.from_numpy(x.copy()), torch.from_numpy(y.copy())
+
+
+@functools.lru_cache(maxsize=None)
+def _stat_pair(oracle_mod, C, k, stat, dt, ff):
+    """(x, y, mean) of the whole stream; with ff = k - 1 its first frames are the history of the rest."""
+    x = _sig(oracle_mod, C, dt, FR3)
+    hist, sig = (x[:ff * C], x[ff * C:]) if ff else (None, x)
+    if dt == "i16":
+        y, m = stat_ref.stat_ref_i16(sig, k, stat, C, hist)
+    else:
+        y, m, _ = stat_ref.stat_ref_f32(sig, k, stat, C, hist)
+    pad = np.full(ff * C, 7.0, np.float32)
+    y, m = (np.concatenate([pad, np.asarray(a, dtype=np.float32).reshape(-1)]) for a in (y, m))
+    return torch.from_numpy(x.copy()), torch.from_numpy(y), torch.from_numpy(m)
+
+
+def _flip(t, i, bit=0):
+    t = t.clone()
+    t.view(torch.int16 if t.dtype == torch.int16 else torch.int32)[i] ^= 1 << bit
+    return t
+
+
+@pytest.mark.parametrize("dt", ["i16", "f32"])
+@pytest.mark.parametrize("k,hop,phase", DECIM)
+@pytest.mark.parametrize("C", CS)
+def test_decim_reference_equals_the_sliced_oracle(oracle_mod, C, k, hop, phase, dt):
+    for ff in (0, k - 1):
+        x, y = _decim_pair(oracle_mod, C, k, hop, phase, dt, ff)
+        assert y.numel() == len(range(phase, FR2 - ff, hop)) * C
+        for chunk in CH2:
+            assert chunked_decim_mismatches(x, y, k, C, hop, phase, chunk, first_frame=ff) == (0, None), (ff, chunk)
+
+
+@pytest.mark.parametrize("dt", ["i16", "f32"])
+@pytest.mark.parametrize("C,k,hop,phase", [(1, 7, 2, 1), (2, 1500, 160, 80), (3, 100, 700, 699), (8, 1500, 3, 1)])
+def test_decim_single_tampered_output_is_reported_at_its_index(oracle_mod, C, k, hop, phase, dt):
+    for ff in (0, k - 1):
+        x, y = _decim_pair(oracle_mod, C, k, hop, phase, dt, ff)
+        n = y.numel()
+        for chunk in CH2:
+            # the first kept frame of the middle chunk: the first m with ff + phase + m * hop >= its start
+            f0 = ff + ((FR2 - ff) // chunk // 2) * chunk
+            m = max(0, -(-(f0 - ff - phase) // hop))
+            assert m * C < n and ff + phase + m * hop >= f0 > ff + phase + (m - 1) * hop
+            for i in (0, m * C - 1, m * C, m * C + C - 1, n - 1):
+                got = chunked_decim_mismatches(x, _flip(y, i), k, C, hop, phase, chunk, first_frame=ff)
+                assert got == (1, i), (ff, chunk, i)
+        y3 = _flip(_flip(_flip(y, n - 1), n // 2), C)
+        assert chunked_decim_mismatches(x, y3, k, C, hop, phase, CH2[1], first_frame=ff) == (3, C)
+
+
+@pytest.mark.parametrize("dt", ["i16", "f32"])
+@pytest.mark.parametrize("C", CS)
+def test_cascade_reference_equals_the_oracle_applied_passes_times(oracle_mod, C, dt):
+    for k, passes in CASC[dt]:
+        x, y = _cascade_pair(oracle_mod, C, k, passes, dt)
+        ff = passes * (k - 1)
+        junk = y.clone()
+        junk[:ff * C] = 21
+        for chunk in CH2:
+            assert chunked_cascade_mismatches(x, y, k, C, passes, chunk) == (0, None), (k, passes, chunk)
+            assert chunked_cascade_mismatches(x, junk, k, C, passes, chunk, first_frame=ff) == (0, None), (k, passes, chunk)
+
+
+@pytest.mark.parametrize("dt,C,k,passes", [("i16", 1, 33, 2), ("i16", 2, 600, 3), ("i16", 3, 100, 3), ("f32", 2, 64, 4),
+                                           ("f32", 8, 1024, 2)])
+def test_cascade_single_tampered_output_is_reported_at_its_index(oracle_mod, dt, C, k, passes):
+    x, y = _cascade_pair(oracle_mod, C, k, passes, dt)
+    n = x.numel()
+    ff = passes * (k - 1)
+    for chunk in CH2:
+        mid = (-(-FR2 // chunk) // 2) * chunk * C
+        for i in (0, mid - 1, mid, n - 1):
+            assert chunked_cascade_mismatches(x, _flip(y, i), k, C, passes, chunk) == (1, i), (chunk, i)
+        # the history form: the frame before first_frame is not looked at, first_frame is
+        assert chunked_cascade_mismatches(x, _flip(y, ff * C - 1), k, C, passes, chunk, first_frame=ff) == (0, None)
+        assert chunked_cascade_mismatches(x, _flip(y, ff * C), k, C, passes, chunk, first_frame=ff) == (1, ff * C)
+        assert chunked_cascade_mismatches(x, _flip(y, n - 1), k, C, passes, chunk, first_frame=ff) == (1, n - 1)
+
+
+@pytest.mark.parametrize("dt", ["i16", "f32"])
+@pytest.mark.parametrize("k", (2, 7, 300))
+@pytest.mark.parametrize("C", CS)
+def test_stat_reference_equals_stat_ref(oracle_mod, C, k, dt):
+    for stat in (stat_ref.MEANSQ, stat_ref.RMS, stat_ref.VAR, stat_ref.STD):
+        for ff in (0, k - 1):
+            x, y, m = _stat_pair(oracle_mod, C, k, stat, dt, ff)
+            for chunk in CH3:
+                for mean in (None, m):
+                    got = chunked_stat_mismatches(x, y, mean, k, C, stat, chunk, first_frame=ff)
+                    assert got == (0, None), (stat, ff, chunk, mean is not None)
+
+
+@pytest.mark.parametrize("dt", ["i16", "f32"])
+@pytest.mark.parametrize("C,k,stat", [(1, 7, stat_ref.STD), (2, 300, stat_ref.VAR), (3, 300, stat_ref.RMS), (8, 2, stat_ref.MEANSQ)])
+def test_stat_single_tampered_output_or_mean_is_reported_at_its_index(oracle_mod, C, k, stat, dt):
+    """Bit 20 of the fp32 pattern: a quarter of the value and more, far outside either bar."""
+    for ff in (0, k - 1):
+        x, y, m = _stat_pair(oracle_mod, C, k, stat, dt, ff)
+        n = x.numel()
+        for chunk in CH3:
+            mid = ff * C + ((FR3 - ff) // chunk // 2) * chunk * C
+            for i in (ff * C, mid - 1, mid, n - 1):
+                assert y[i] != 0 and m[i] != 0          # (a flipped bit of 0.0f is a subnormal)
+                assert chunked_stat_mismatches(x, _flip(y, i, 20), m, k, C, stat, chunk, first_frame=ff) == (1, i), (ff, chunk, i)
+                assert chunked_stat_mismatches(x, _flip(y, i, 20), None, k, C, stat, chunk, first_frame=ff) == (1, i)
+                assert chunked_stat_mismatches(x, y, _flip(m, i, 20), k, C, stat, chunk, first_frame=ff) == (1, i), (ff, chunk, i)
+            if ff:
+                bad = _flip(y, ff * C - 1, 20)
+                assert chunked_stat_mismatches(x, bad, _flip(m, ff * C - 1, 20), k, C, stat, chunk, first_frame=ff) == (0, None)
+        # an output and a mean of one sample count once; the index is the lowest
+        got = chunked_stat_mismatches(x, _flip(_flip(y, n - 1, 20), n // 2, 20), _flip(m, n // 2, 20), k, C, stat, CH3[1], first_frame=ff)
+        assert got == (2, n // 2)
+
+
+def test_stat_bars_are_stat_refs(oracle_mod):
+    """int16: one fp32 ulp passes, two do not, and a reference of 0 takes only 0.0f.  fp32: the
+    1e-5 bars of check_f32, just inside and just outside."""
+    k, C = 100, 1
+    x, y, m = _stat_pair(oracle_mod, C, k, stat_ref.STD, "i16", 0)
+    i = 1234
+    inf = torch.tensor(float("inf"))
+    up1 = y.clone()
+    up1[i] = torch.nextafter(y[i], inf)
+    up2 = up1.clone()
+    up2[i] = torch.nextafter(up1[i], inf)
+    assert chunked_stat_mismatches(x, up1, m, k, C, stat_ref.STD, 1024) == (0, None)
+    assert chunked_stat_mismatches(x, up2, m, k, C, stat_ref.STD, 1024) == (1, i)
+    m1, m2 = m.clone(), m.clone()                   # the mean's bar is the same
+    m1[i] = torch.nextafter(m[i], inf)
+    m2[i] = torch.nextafter(m1[i], inf)
+    assert chunked_stat_mismatches(x, y, m1, k, C, stat_ref.STD, 1024) == (0, None)
+    assert chunked_stat_mismatches(x, y, m2, k, C, stat_ref.STD, 1024) == (1, i)
+    const = torch.full((4096,), 12345, dtype=torch.int16)
+    zero = torch.zeros(4096)
+    zero[:k - 1] = torch.from_numpy(stat_ref.stat_ref_i16(const.numpy(), k, stat_ref.VAR)[0][:k - 1, 0])
+    assert chunked_stat_mismatches(const, zero, None, k, C, stat_ref.VAR, 1000) == (0, None)
+    tiny = zero.clone()
+    tiny[2000] = 1e-30
+    assert chunked_stat_mismatches(const, tiny, None, k, C, stat_ref.VAR, 1000) == (1, 2000)
+    for stat in (stat_ref.MEANSQ, stat_ref.VAR):
+        x, y, m = _stat_pair(oracle_mod, 2, k, stat, "f32", 0)
+        _, _, M = stat_ref.stat_ref_f32(x.numpy(), k, stat, 2)
+        j = 2 * 3000 + 1
+        inside, outside = y.clone(), y.clone()
+        inside[j] = y[j] + np.float32(0.9e-5 * M.reshape(-1)[j])
+        outside[j] = y[j] + np.float32(1.2e-5 * M.reshape(-1)[j])
+        assert chunked_stat_mismatches(x, inside, m, k, 2, stat, 1024) == (0, None)
+        assert chunked_stat_mismatches(x, outside, m, k, 2, stat, 1024) == (1, j)
+
+
+def test_siblings_reject_what_they_cannot_check():
+    xi = torch.zeros(12, dtype=torch.int16)
+    xf = torch.zeros(12, dtype=torch.float32)
+    with pytest.raises(ValueError):
+        chunked_decim_mismatches(xi, xi[:6], 2, 1, 2, 2, 8)                # phase outside [0, hop)
+    with pytest.raises(ValueError):
+        chunked_decim_mismatches(xi, xi[:5], 2, 1, 2, 0, 8)                # not M * C samples
+    with pytest.raises(ValueError):
+        chunked_decim_mismatches(xf + 0.5, xf[:6], 2, 1, 2, 0, 8)          # fp32 sums would not be exact
+    with pytest.raises(TypeError):
+        chunked_decim_mismatches(xf.double(), xf.double()[:6], 2, 1, 2, 0, 8)
+    with pytest.raises(ValueError):
+        chunked_cascade_mismatches(xf, xf, 3, 1, 2, 8)                     # fp32: k not a power of two
+    with pytest.raises(ValueError):
+        chunked_cascade_mismatches(xf, xf, 2048, 1, 3, 8)                  # fp32: log2(k) * passes > 30
+    with pytest.raises(ValueError):
+        chunked_cascade_mismatches(xf + 0.5, xf, 2, 1, 2, 8)               # fp32: not integer-valued
+    with pytest.raises(ValueError):
+        chunked_cascade_mismatches(xi, xi, 3, 1, 0, 8)                     # passes < 1
+    assert chunked_cascade_mismatches(xi, xi, 3, 1, 2, 8) == (0, None)     # int16: any k
+    with pytest.raises(ValueError):
+        chunked_stat_mismatches(xi, xf, None, 65536, 1, 0, 8)              # N would leave int64
+    with pytest.raises(ValueError):
+        chunked_stat_mismatches(xi, xi, None, 2, 1, 0, 8)                  # the output is fp32
+    with pytest.raises(ValueError):
+        chunked_stat_mismatches(xi, xf, xf[:6], 2, 1, 0, 8)                # mean of another size
+    with pytest.raises(ValueError):
+        chunked_stat_mismatches(xi, xf, None, 2, 1, 4, 8)                  # stat outside 0..3
+    with pytest.raises(ValueError):
+        chunked_stat_mismatches(xf + 0.5, xf, None, 2, 1, 0, 8)            # fp32: not integer-valued
+    with pytest.raises(ValueError):
+        chunked_stat_mismatches(xi, xf, None, 2, 5, 0, 8)                  # partial frame

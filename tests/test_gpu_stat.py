@@ -320,3 +320,135 @@ def test_short_signals(gpu, oracle_mod, kind, C, frames):
             run(gpu, case, stat, TILE, with_mean=stat == STD)
         case = case_of(oracle_mod, kind, C, frames, k, with_hist=True)
         run(gpu, case, VAR, TILE, with_mean=True, off_out=1)
+
+
+# ---- the fp32 dynamic-range clauses of include/mavg.h on a signal that falls silent ----
+# Four tiles plus 17 frames: one and a half tiles near 1e15 (squares near 1e30), the rest near 1e-3
+# (stat_ref.falls_silent: 360 dB down).  The reference is stat_ref's exact window sums (no residue of
+# the loud prefix; tests/test_stat_model.py checks that and runs the kernels' models on this signal).
+class Silent:
+    """The signal at (C, k), its exact references and what the bounds need, computed once."""
+
+    def __init__(self, oracle, C, k):
+        self.C, self.k = C, k
+        plan = plan_of("f32d2", C, 1 << 16, k, VAR)
+        assert plan.startswith(TILE), plan
+        self.TF = tile_frames(plan)
+        assert k <= self.TF                      # a tile that starts a full tile after the edge has a quiet halo
+        self.frames, self.loud = 4 * self.TF + 17, self.TF + self.TF // 2
+        self.case = Case(oracle, "f32d2", C, self.frames, k, False,
+                         x=stat_ref.falls_silent(oracle, C, self.frames, self.loud, seed=C))
+        x = self.case.x
+        assert np.abs(x[:self.loud * C]).min() >= 0.4e15 and np.abs(x[self.loud * C:]).max() <= 2e-3
+        self.S2 = stat_ref.window_sums(x, k, C)[1]
+        self.mean_abs = stat_ref.window_sums(np.abs(x), k, C)[0] / k
+        x64 = x.astype(np.float64).reshape(-1, C)
+        self.sq = np.concatenate([np.zeros((k, C)), x64 * x64])      # sq[k + f] = x[f]^2
+
+    def check(self, stat, y, mean, rows, what):
+        """The ordinary bars on the frames `rows` (a slice), each against its own window's mean square."""
+        ref, m, M = self.case.ref(stat)
+        stat_ref.check_f32(stat, y[rows], ref[rows], M[rows], what)
+        if mean is not None:
+            bad = ~(np.abs(mean[rows].astype(np.float64) - m[rows]) <= 1e-5 * np.maximum(np.abs(m[rows]), self.mean_abs[rows]))
+            assert not bad.any(), (what, "mean", int(bad.sum()), tuple(np.argwhere(bad)[0]))
+
+    def terms(self, f0, f1):
+        """(sum of |terms| per channel, number of terms) the tile or strip [f0, f1) adds: the k squares
+        in front of it, then x^2 and x[n-k]^2 per frame."""
+        k, sq = self.k, self.sq
+        return sq[f0:f0 + k].sum(0) + sq[k + f0:k + f1].sum(0) + sq[f0:f1].sum(0), k + 2 * (f1 - f0)
+
+
+_silent = {}
+
+
+def silent_of(oracle, C, k):
+    if (C, k) not in _silent:
+        _silent[(C, k)] = Silent(oracle, C, k)
+    return _silent[(C, k)]
+
+
+def strip_len(plan):
+    return int(re.search(r" L=(\d+) ", plan).group(1))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("k", (2, 7, 16))
+@pytest.mark.parametrize("C", (1, 2))
+def test_short_windows_hold_their_bars_whatever_precedes_them(gpu, oracle_mod, C, k):
+    """Windows of at most 16 frames are summed directly: every frame meets the ordinary bars against
+    its own window's mean square -- the quiet ones right after the edge, and the ones that straddle
+    it (their mean square is the loud one) -- in both unit forms of the tile and on the strip."""
+    s = silent_of(oracle_mod, C, k)
+    every = slice(0, s.frames)
+    for stat in ALL_STATS:
+        for with_mean in (False, True):
+            what = ("falls silent", C, k, stat, with_mean)
+            for off_in in (0, 1):
+                y, mean = run(gpu, s.case, stat, TILE, with_mean=with_mean, off_in=off_in, x=s.case.x)
+                s.check(stat, y, mean, every, what + ("tile", off_in))
+            with forced_strip() as lib:
+                y, mean = run(gpu, s.case, stat, STRIP, with_mean=with_mean, library=lib, x=s.case.x)
+            s.check(stat, y, mean, every, what + ("strip",))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("path", ("tile", "strip"))
+@pytest.mark.parametrize("k", (17, 100, 1024))
+@pytest.mark.parametrize("C", (1, 2))
+def test_long_windows_keep_a_local_residue_of_the_loud_part(gpu, oracle_mod, C, k, path):
+    """Running sums (k > 16).  (a) the clamp: no NaN, VAR >= 0, STD finite and >= 0 everywhere.
+    (b) the residue is local: the sums restart per tile from a direct halo sum (per strip from the
+    window in front of it), so a tile whose halo is quiet -- every tile that starts a full tile after
+    the last loud frame -- and a strip that starts k frames after it meet the ordinary bars.
+    (c) elsewhere the implied window sum of squares y k (MEANSQ) obeys the textbook summation bound
+    N 2^-53 Sigma + 2^-24 y k over the N terms that tile or strip adds, Sigma the sum of their absolute
+    values: derived, and loose -- a float accumulator or a lost halo term misses it by nine orders
+    of magnitude (tests/test_stat_model.py shows both).  (d) prints the measured residue."""
+    s = silent_of(oracle_mod, C, k)
+    family = TILE if path == "tile" else STRIP
+    with (forced(0) if path == "tile" else forced_strip()) as lib:     # the tile by the rule, on the release build
+        lib = None if path == "tile" else lib
+        plan = plan_of("f32d2", C, s.frames, k, MEANSQ, library=lib)
+        assert plan.startswith(family) and " direct" not in plan, plan
+        unit = tile_frames(plan) if path == "tile" else strip_len(plan)
+        assert path == "strip" or unit == s.TF
+        units = [(f0, min(f0 + unit, s.frames)) for f0 in range(0, s.frames, unit)]
+        quiet = [(f0, f1) for f0, f1 in units if f0 - k >= s.loud]
+        assert len(quiet) >= 2 and (path == "strip" or (3 * s.TF, 4 * s.TF) in quiet)
+        for stat in ALL_STATS:
+            with_mean = stat in (VAR, STD)
+            y, mean = run(gpu, s.case, stat, family, with_mean=with_mean, library=lib, x=s.case.x)
+            what = ("falls silent", C, k, stat, path)
+            assert np.isfinite(y).all() and (y >= 0).all(), what                       # (a)
+            assert mean is None or np.isfinite(mean).all(), what
+            for f0, f1 in quiet:                                                        # (b)
+                s.check(stat, y, mean, slice(f0, f1), what + (f0,))
+            if stat != MEANSQ:
+                continue
+            worst, clamped = 0.0, 0
+            for f0, f1 in units:                                                        # (c), every tile or strip
+                sigma, n = s.terms(f0, f1)
+                bad = stat_ref.summation_bound(y[f0:f1], k, s.S2[f0:f1], sigma, n)
+                assert not bad.any(), (what, f0, int(bad.sum()), tuple(np.argwhere(bad)[0]))
+                # (d) the residue beside the largest window sum the unit's running sums pass through
+                # (the window in front of it included); a residue below zero leaves as 0.0f
+                yk = y[f0:f1].astype(np.float64) * k
+                err = np.maximum(np.abs(yk - s.S2[f0:f1]) - 2.0 ** -24 * yk, 0.0)
+                big = s.S2[max(f0 - 1, 0):f1].max(0)
+                worst = max(worst, float((err / big).max()))
+                clamped += int(((y[f0:f1] == 0) & (s.S2[f0:f1] > 0)).sum())
+            print(f"falls silent C={C} k={k} {path}: max |error of y k beyond its fp32 rounding| / "
+                  f"(largest window sum of squares in the {path}) = {worst:.3e}; {clamped} outputs clamped to 0")
+
+
+def test_the_direct_sums_end_at_16_frames():
+    """The plan says which windows are summed directly: grade 16 is, grade 17 is not, on both kernels."""
+    for C in (1, 2):
+        for lib, family in ((None, TILE), (HOOKS_LIB, STRIP)):
+            with (forced_strip() if lib else forced(0)):
+                p16, p17 = (plan_of("f32d2", C, 1 << 14, k, VAR, True, lib) for k in (16, 17))
+            assert p16.startswith(family) and p17.startswith(family), (p16, p17)
+            assert p16.endswith(" direct") and " direct" not in p17, (p16, p17)
+            assert " direct" not in plan_of("i16", C, 1 << 14, 16, VAR, True)

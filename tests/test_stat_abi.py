@@ -48,7 +48,8 @@ def test_header_declares_the_enum_and_strerror_is_unchanged():
     assert m, "mavg_stat enum"
     vals = dict(re.findall(r"(MAVG_STAT_\w+)\s*=\s*(\d+)", m.group(1)))
     assert vals == {"MAVG_STAT_MEANSQ": "0", "MAVG_STAT_RMS": "1", "MAVG_STAT_VAR": "2", "MAVG_STAT_STD": "3"}
-    assert "NOT tested past 2^31 samples" in h[h.index("Moving second moment"):h.index("} mavg_stat;")]
+    block = h[h.index("Moving second moment"):h.index("} mavg_stat;")]
+    assert "NOT tested past 2^31 samples" not in block and "tests/test_gpu_bigsignal.py" in block
     assert [_lib.strerror(s) for s in range(7)] == [
         "ok", "invalid argument", "unsupported configuration", "pointer not aligned to the sample size",
         "workspace too small", "HIP runtime error", "unknown status"]

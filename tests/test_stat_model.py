@@ -191,3 +191,58 @@ def test_strip_model_with_a_boundary_inside_the_warm_up(k, L, with_hist):
     assert S1 == D1 and S2 == D2
     T1, T2 = tile_model(x, k, 32, hist)               # and the two kernels' sums agree exactly
     assert [int(v) for v in T1] == S1 and [int(v) for v in T2] == S2
+
+
+# ---- a signal that falls silent: what include/mavg.h promises fp32 windows of more than 16 frames ----
+def _meansq32(S2, k):
+    """stat_value for MEANSQ: the clamp, then fp32."""
+    return np.maximum(np.asarray(S2, dtype=np.float64) / k, 0.0).astype(np.float32)
+
+
+@pytest.mark.parametrize("k", (17, 100, 256))
+def test_models_on_a_signal_that_falls_silent(oracle_mod, k):
+    """One and a half tiles near 1e15, then about 1e-3.  The exact reference first: its quiet
+    windows equal a direct float64 sum (no residue of the loud prefix).  Then the tile model (running
+    sums restarted per tile from the halo's direct sum) and the strip model (restarted per strip):
+    (b) a tile whose halo is quiet -- it starts k frames or more after the last loud frame, so every
+        tile that starts a full tile after it -- meets the ordinary bars against its own mean square;
+        so does every strip that starts k frames or more after it;
+    (c) everywhere else the implied window sum obeys the textbook bound over the terms that tile
+        (strip) adds: the halo's k squares, then x^2 and x[n-k]^2 per frame."""
+    TF = 256
+    L = min(max(k // 4, 16), 2048)
+    frames, loud = 4 * TF + 17, TF + TF // 2
+    x = stat_ref.falls_silent(oracle_mod, 1, frames, loud)
+    assert np.abs(x[:loud]).min() >= 0.4e15 and np.abs(x[loud:]).max() <= 2e-3
+    ref, _, M = stat_ref.stat_ref_f32(x, k, stat_ref.MEANSQ)
+    S2 = M[:, 0] * k
+    x64 = x.astype(np.float64)
+    for f in range(loud + k - 1, frames, 37):         # windows wholly in the quiet part, summed directly
+        d = float(np.sum(x64[f - k + 1:f + 1] ** 2))
+        assert abs(S2[f] - d) <= 1e-12 * d, (f, S2[f], d)
+    sq = np.concatenate([np.zeros(k), x64 * x64])     # sq[k + f] = x[f]^2, zeros in front
+
+    def terms(f0, f1):
+        """(sum of |terms|, number of terms) the unit [f0, f1) adds: its halo, then x^2 and x[n-k]^2 per frame."""
+        return sq[f0:f0 + k].sum() + sq[k + f0:k + f1].sum() + sq[f0:f1].sum(), k + 2 * (f1 - f0)
+
+    for name, unit, (_, T2) in (("tile", TF, tile_model(x, k, TF)), ("strip", L, strip_model(x, k, L))):
+        y = _meansq32(T2, k)
+        assert np.isfinite(y).all() and (y >= 0).all()
+        quiet_units = 0
+        for f0 in range(0, frames, unit):
+            f1 = min(f0 + unit, frames)
+            if f0 - k >= loud:
+                quiet_units += 1
+                stat_ref.check_f32(stat_ref.MEANSQ, y[f0:f1, None], ref[f0:f1], M[f0:f1], (name, k, f0))
+            sigma, n = terms(f0, f1)
+            bad = stat_ref.summation_bound(y[f0:f1], k, S2[f0:f1], sigma, n)
+            assert not bad.any(), (name, k, f0, int(bad.sum()))
+        assert quiet_units >= 2, (name, quiet_units)
+    # the bound is not vacuous: a float32 accumulator, or a halo sum that lost its loudest term, misses it
+    f0 = TF
+    sigma, n = terms(f0, 2 * TF)
+    P32 = np.concatenate([np.zeros(k, np.float32), np.cumsum(x * x, dtype=np.float32)])
+    assert stat_ref.summation_bound(_meansq32((P32[k:] - P32[:-k])[f0:2 * TF], k), k, S2[f0:2 * TF], sigma, n).any()
+    lost = np.asarray(tile_model(x, k, TF)[1][f0:2 * TF]) - sq[f0:f0 + k].max()
+    assert stat_ref.summation_bound(_meansq32(lost, k), k, S2[f0:2 * TF], sigma, n).any()
