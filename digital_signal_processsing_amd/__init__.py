@@ -11,6 +11,7 @@ only for device memory and streams.
     y = moving_average_ragged(x, grade=1024, lengths=[5, 0, 30011, 7])   # packed rows of different lengths
     y = moving_average_decimated(x, grade=400, hop=160)  # only every hop-th output frame, in one launch
     y = moving_rms(x, grade=1024)                      # fp32 RMS / variance / std of the window, one launch
+    lo, hi = moving_minmax(x, grade=1024)              # the window's minimum and maximum (peak envelope), one launch
 
 Semantics: ``basics/profilable_moving_averager.cpp:14-37`` -- interleaved
 frames, window ``grade`` frames, zero history (or ``history``: the
@@ -53,6 +54,11 @@ __all__ = [
     "moving_mean_square",
     "stat_plan",
     "STATS",
+    "moving_max",
+    "moving_min",
+    "moving_minmax",
+    "moving_extrema_into",
+    "extrema_plan",
     "fill_synthetic",
     "workspace_bytes",
     "resolve_algo",
@@ -729,6 +735,88 @@ def moving_variance(x, grade: int, channels: int = 1, **kw):
 def moving_std(x, grade: int, channels: int = 1, **kw):
     """``moving_stat(x, grade, "std", ...)``: the window's population standard deviation."""
     return moving_stat(x, grade, "std", channels, **kw)
+
+
+def extrema_plan(n: int, grade: int, channels: int = 1, dtype: int = F32, with_max: bool = True, with_min: bool = True,
+                 library: Optional[str] = None, aligned: bool = True) -> str:
+    """What mavg_extrema_run would do (nothing is launched): ``extrema_tile<...> ... tile_frames=N ...``
+    or ``extrema_strip ... L=...``.  ``aligned=False``: for views off 16-B alignment (the frame-unit
+    form, ``F=1``)."""
+    import ctypes
+    buf = ctypes.create_string_buffer(512)
+    given = 1 if aligned else 3    # bit 1: views off 16-B alignment
+    _lib.check(_lib.load(library).mavg_extrema_plan(n, channels, grade, dtype, given if with_max else 0,
+                                                    given if with_min else 0, buf, len(buf)), "mavg_extrema_plan")
+    return buf.value.decode()
+
+
+def moving_extrema_into(x, max_out, min_out, grade: int, channels: int = 1, history=None, stream=None,
+                        library: Optional[str] = None) -> None:
+    """Enqueue the moving maximum and / or minimum of ``x`` on ``stream`` (default: current), one
+    launch, no workspace.
+
+    ``max_out`` and ``min_out``: contiguous device tensors of ``x``'s dtype and size that overlap
+    neither ``x`` nor each other; either may be ``None``, not both.  ``history``: the
+    ``(grade-1) * channels`` samples in front of ``x``; without one the window is truncated at
+    frame 0 (pass zeros for zero padding)."""
+    frames, C = _decim_shape(x, channels)
+    dt = _dtype_code(x)
+    if max_out is None and min_out is None:
+        raise ValueError("max_out and min_out must not both be None")
+    for t, what in ((max_out, "max_out"), (min_out, "min_out")):
+        if t is None:
+            continue
+        if t.dtype != x.dtype:
+            raise ValueError(f"{what} must have x's dtype {x.dtype} (an extremum is one of the samples), got {t.dtype}")
+        if t.numel() != x.numel():
+            raise ValueError(f"{what} must hold x's {x.numel()} samples, got {t.numel()}")
+    for t in (max_out, min_out):
+        if t is not None:
+            _check_device_pair(x, t)
+    hist_ptr = _history_ptr(history, x, (grade - 1) * C, "(grade-1)*channels")
+    st = _lib.load(library).mavg_extrema_run(x.data_ptr(), max_out.data_ptr() if max_out is not None else None,
+                                             min_out.data_ptr() if min_out is not None else None, x.numel(), C, grade,
+                                             dt, hist_ptr, _stream_handle(stream, x.device))
+    _lib.check(st, "mavg_extrema_run")
+
+
+def _moving_extrema(x, grade: int, channels: int, history, stream, library, want_max: bool, want_min: bool):
+    torch = _torch()
+    _check_device_x(x)
+    _decim_shape(x, channels)
+    _dtype_code(x)
+    C = channels if x.dim() == 1 else x.shape[1]
+    second = []
+
+    def into(out):
+        if want_max and want_min:
+            second.append(_on_stream(stream, lambda: torch.empty_like(out)))
+            moving_extrema_into(x, second[0], out, grade, C, history, stream, library)
+        elif want_max:
+            moving_extrema_into(x, out, None, grade, C, history, stream, library)
+        else:
+            moving_extrema_into(x, None, out, grade, C, history, stream, library)
+
+    out = _with_out(x, stream, into, (x, history))
+    return (out, second[0]) if second else out
+
+
+def moving_max(x, grade: int, channels: int = 1, history=None, stream=None, library: Optional[str] = None):
+    """Per channel the largest sample of the causal ``grade``-frame window of ``x`` (fp32 or int16),
+    in ``x``'s dtype and shape: a peak envelope, ``rolling(grade).max()``, a 1-D dilation.  Without
+    ``history`` the window is truncated at frame 0."""
+    return _moving_extrema(x, grade, channels, history, stream, library, True, False)
+
+
+def moving_min(x, grade: int, channels: int = 1, history=None, stream=None, library: Optional[str] = None):
+    """Per channel the smallest sample of the causal ``grade``-frame window of ``x``; see ``moving_max``."""
+    return _moving_extrema(x, grade, channels, history, stream, library, False, True)
+
+
+def moving_minmax(x, grade: int, channels: int = 1, history=None, stream=None, library: Optional[str] = None):
+    """``(min, max)`` of the causal ``grade``-frame window from one launch and one read of ``x``
+    (peak-to-peak is ``max - min``; the absolute peak ``maximum(max, -min)``)."""
+    return _moving_extrema(x, grade, channels, history, stream, library, True, True)
 
 
 def fill_synthetic(n: int, dtype=None, seed: int = 0x5EED, offset: int = 0, dist: int = 0,

@@ -68,6 +68,8 @@ EXPORTED_SYMBOLS = (
     "mavg_cascade_plan",
     "mavg_stat_run",
     "mavg_stat_plan",
+    "mavg_extrema_run",
+    "mavg_extrema_plan",
     "mavg_resolve_algo",
     "mavg_plan",
     "mavg_fill_synthetic",
@@ -79,7 +81,7 @@ EXPORTED_SYMBOLS = (
 )
 # exported by the debug build only (include/mavg_debug.h)
 DEBUG_SYMBOLS = ("mavg_test_ahead_schedule", "mavg_debug_force_decim", "mavg_debug_force_cascade",
-                 "mavg_debug_force_stat")
+                 "mavg_debug_force_stat", "mavg_debug_force_extrema")
 # mavg_debug_force_decim's paths (include/mavg_debug.h)
 DECIM_AUTO, DECIM_SCAN, DECIM_WINDOW, DECIM_FULL = 0, 1, 2, 3
 # mavg_debug_force_cascade's paths (include/mavg_debug.h)
@@ -89,6 +91,8 @@ STAT_MEANSQ, STAT_RMS, STAT_VAR, STAT_STD = 0, 1, 2, 3
 STATS = {"meansq": STAT_MEANSQ, "rms": STAT_RMS, "var": STAT_VAR, "std": STAT_STD}
 # mavg_debug_force_stat's paths (include/mavg_debug.h)
 STAT_AUTO, STAT_TILE, STAT_STRIP = 0, 1, 2
+# mavg_debug_force_extrema's paths (include/mavg_debug.h)
+EXTREMA_AUTO, EXTREMA_TILE, EXTREMA_STRIP = 0, 1, 2
 ABI_VERSION = 4
 DEBUG_LIB_PATH = os.path.join(_PKG, "lib", "libmavg_debug.so")
 # release flags + the test hooks (the forced-schedule parity tests time nothing, but they run the
@@ -170,6 +174,13 @@ def load(path: str = None) -> ctypes.CDLL:
     if hasattr(lib, "mavg_debug_force_stat"):  # debug and hooks builds only
         lib.mavg_debug_force_stat.argtypes = [i]
         lib.mavg_debug_force_stat.restype = i
+    lib.mavg_extrema_run.argtypes = [vp, vp, vp, sz, i, i, i, vp, vp]
+    lib.mavg_extrema_run.restype = i
+    lib.mavg_extrema_plan.argtypes = [sz, i, i, i, i, i, ctypes.c_char_p, sz]
+    lib.mavg_extrema_plan.restype = i
+    if hasattr(lib, "mavg_debug_force_extrema"):  # debug and hooks builds only
+        lib.mavg_debug_force_extrema.argtypes = [i]
+        lib.mavg_debug_force_extrema.restype = i
     lib.mavg_resolve_algo.argtypes = [sz, i, i, i, i]
     lib.mavg_resolve_algo.restype = i
     lib.mavg_plan.argtypes = [sz, i, i, i, i, i, ctypes.c_char_p, sz]

@@ -538,6 +538,41 @@ int stat_launch(int path, const StatCall& a, hipStream_t s) {
   return stat_tile_any(a.dtype, a.C, ss, a.k, a.stat, s);
 }
 
+// ---- extrema (mavg_extrema_run) --------------------------------------------------------------
+// The dispatch rule, in the order mavg.h gives; *path = kExtremaTile / kExtremaStrip: the tile
+// kernel wherever it takes the window (extrema_tile_fits).  The test hook's forced path replaces
+// the rule: MAVG_ERR_UNSUPPORTED where the tile kernel cannot take the shape.
+int extrema_path(int C, int k, int dtype, int* path) {
+  const bool tile_ok = extrema_tile_fits(dtype, C, k);
+  int forced = kExtremaAuto;
+#ifdef MAVG_TEST_HOOKS
+  forced = g_test_extrema_path.load(std::memory_order_relaxed);
+#endif
+  if (forced == kExtremaTile && !tile_ok) return MAVG_ERR_UNSUPPORTED;
+  *path = forced != kExtremaAuto ? forced : tile_ok ? kExtremaTile : kExtremaStrip;
+  return MAVG_OK;
+}
+
+struct ExtremaCall {
+  const void* in;
+  void* omax;
+  void* omin;
+  const void* hist;
+  size_t n;
+  int C, k, dtype;
+};
+
+// The one launch of extrema_tile / extrema_strip (plan mode when g_plan is set); views of any
+// sample alignment: the 16-B-unit form when the input and every given output are 16-B aligned,
+// else the frame-unit form over the whole signal (no head is peeled).
+int extrema_launch(int path, const ExtremaCall& a, hipStream_t s) {
+  ExtremaSig es{a.in, a.omax, a.omin, a.hist, a.n / (size_t)a.C};
+  if (path == kExtremaStrip) return extrema_strip_any(a.dtype, a.C, es, a.k, s);
+  es.unit = aligned(a.in, 16) && (a.omax == nullptr || aligned(a.omax, 16)) && (a.omin == nullptr || aligned(a.omin, 16));
+  es.eio = !es.unit && !aligned(a.in, elem_size(a.dtype) * (size_t)a.C) ? 1 : 0;
+  return extrema_tile_any(a.dtype, a.C, es, a.k, s);
+}
+
 // cascade_loop's workspace, in this order: the ping-pong buffer (the signal's bytes, 16-B padded);
 // with a history two block buffers of passes * (grade - 1) * C samples each (16-B padded); then
 // mavg_run's own workspace -- the signal's, and with a history at least the first block's.
@@ -971,6 +1006,46 @@ int mavg_stat_run(const void* d_in, float* d_out, float* d_mean, size_t n_sample
   if (st != MAVG_OK) return st;
   return stat_launch(path, StatCall{d_in, d_out, d_mean, d_history, n_samples, channels, grade, stat, dtype},
                      static_cast<hipStream_t>(stream));
+}
+
+int mavg_extrema_plan(size_t n_samples, int channels, int grade, int dtype, int with_max, int with_min, char* buf,
+                      size_t buflen) {
+  if (buf == nullptr || buflen == 0) return MAVG_ERR_INVALID_ARG;
+  buf[0] = 0;
+  int st = validate(n_samples, channels, grade, dtype, MAVG_ALGO_AUTO, 0);
+  if (st != MAVG_OK) return st;
+  if (with_max == 0 && with_min == 0) return MAVG_ERR_INVALID_ARG;
+  if (n_samples == 0) return MAVG_ERR_INVALID_ARG;  // nothing to describe, as mavg_plan
+  int path = kExtremaStrip;
+  st = extrema_path(channels, grade, dtype, &path);
+  if (st != MAVG_OK) return st;
+  PlanScope ps;
+  void* const omax = with_max != 0 ? kPlanOut : nullptr;
+  void* const omin = with_min != 0 ? const_cast<void*>(kPlanOff) : nullptr;
+  // (bit 1 of either flag: views off 16-B alignment -- an input one sample past a 16-B boundary)
+  const bool off = ((with_max | with_min) & 2) != 0;
+  const void* const in = off ? static_cast<const char*>(kPlanIn) + elem_size(dtype) : kPlanIn;
+  st = extrema_launch(path, ExtremaCall{in, omax, omin, nullptr, n_samples, channels, grade, dtype}, nullptr);
+  if (st == MAVG_OK) snprintf(buf, buflen, "%s", ps.plan.text);
+  return st;
+}
+
+// One launch: the tile kernel where the rule (extrema_path) takes the window, else the strip kernel.
+int mavg_extrema_run(const void* d_in, void* d_max, void* d_min, size_t n_samples, int channels, int grade, int dtype,
+                     const void* d_history, void* stream) {
+  int st = validate(n_samples, channels, grade, dtype, MAVG_ALGO_AUTO, 0);
+  if (st != MAVG_OK) return st;
+  if (d_max == nullptr && d_min == nullptr) return MAVG_ERR_INVALID_ARG;
+  if (n_samples == 0) return MAVG_OK;
+  if (d_in == nullptr) return MAVG_ERR_INVALID_ARG;
+  const size_t eb = elem_size(dtype);
+  if (!aligned(d_in, eb) || !aligned(d_max, eb) || !aligned(d_min, eb) || (d_history != nullptr && !aligned(d_history, eb)))
+    return MAVG_ERR_MISALIGNED;
+  int path = kExtremaStrip;
+  st = extrema_path(channels, grade, dtype, &path);
+  if (st != MAVG_OK) return st;
+  return extrema_launch(path, ExtremaCall{d_in, d_max, d_min, d_history, n_samples, channels, grade, dtype},
+                        static_cast<hipStream_t>(stream));
 }
 
 int mavg_ragged_workspace_bytes(const int64_t* h_offsets, size_t rows, int channels, int grade, int dtype,

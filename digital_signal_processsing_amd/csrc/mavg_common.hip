@@ -11,6 +11,7 @@ std::atomic<int> g_test_ahead_spin{-1};
 std::atomic<int> g_test_decim_path{kDecimAuto};
 std::atomic<int> g_test_cascade_path{kCascadeAuto};
 std::atomic<int> g_test_stat_path{kStatAuto};
+std::atomic<int> g_test_extrema_path{kExtremaAuto};
 #endif
 
 // ---- per-device attribute cache (no stream work, capture-safe) --------------
@@ -64,6 +65,11 @@ extern "C" int mavg_debug_force_cascade(int path) {
 extern "C" int mavg_debug_force_stat(int path) {
   if (path < mavg::kStatAuto || path > mavg::kStatStrip) return MAVG_ERR_INVALID_ARG;
   mavg::g_test_stat_path.store(path, std::memory_order_relaxed);
+  return MAVG_OK;
+}
+extern "C" int mavg_debug_force_extrema(int path) {
+  if (path < mavg::kExtremaAuto || path > mavg::kExtremaStrip) return MAVG_ERR_INVALID_ARG;
+  mavg::g_test_extrema_path.store(path, std::memory_order_relaxed);
   return MAVG_OK;
 }
 #endif

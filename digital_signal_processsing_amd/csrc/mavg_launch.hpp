@@ -279,6 +279,36 @@ int stat_tile_any(int dtype, int C, const StatSig& ss, int grade, int stat, hipS
 int stat_strip_frames(int grade);
 int stat_strip_any(int dtype, int C, const StatSig& ss, int grade, int stat, hipStream_t st);
 
+// The moving extrema (mavg_extrema.hpp, instantiated in mavg_extrema.hip): the maximum and / or the
+// minimum of the grade-frame window in the input's dtype, one launch; hist holds grade - 1 frames
+// or is NULL; omax or omin may be NULL, not both.
+//   unit  the 16-B-unit form (in and every given output 16-B aligned); else the frame-unit form
+//   eio   frame-unit form on an input that is only element-aligned (UnitIO::gload)
+struct ExtremaSig {
+  const void* in;
+  void* omax;
+  void* omin;
+  const void* hist;
+  size_t nframes;
+  bool unit = true;
+  int eio = 0;
+};
+// The test hook's forced path (mavg_debug_force_extrema, include/mavg_debug.h): 0 = the rule decides
+constexpr int kExtremaAuto = 0, kExtremaTile = 1, kExtremaStrip = 2;
+#ifdef MAVG_TEST_HOOKS
+extern std::atomic<int> g_test_extrema_path;
+#endif
+// Whether the tile kernel takes this window (the dispatch rule, and what a forced extrema_tile may
+// run): channels 1 or 2, grade >= 2, a halo (grade - 1) * C * sample size of at most 16 KiB, and
+// its LDS layout (ExtremaLds, both outputs) inside lds_budget in both forms.
+bool extrema_tile_fits(int dtype, int C, int grade);
+// MAVG_ERR_UNSUPPORTED: the window does not fit, or the launch would exceed grid_too_large
+int extrema_tile_any(int dtype, int C, const ExtremaSig& es, int grade, hipStream_t st);
+// The strip kernel: every channels, grade and sample-aligned view; L = extrema_strip_frames(grade)
+// frames per thread.  MAVG_ERR_UNSUPPORTED: the launch would exceed grid_too_large.
+int extrema_strip_frames(int grade);
+int extrema_strip_any(int dtype, int C, const ExtremaSig& es, int grade, hipStream_t st);
+
 // ceil(k / F): the units a k-frame halo takes (TileParams / AheadParams halo_units)
 template <int F>
 constexpr size_t tile_halo_units(int k) { return (size_t)(((long long)k + F - 1) / F); }

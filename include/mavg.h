@@ -521,6 +521,76 @@ int mavg_stat_run(const void* d_in, float* d_out, float* d_mean /* or NULL */, s
 int mavg_stat_plan(size_t n_samples, int channels, int grade, int stat, int dtype,
                    int with_mean, char* buf, size_t buflen);
 
+/* Moving extrema (peak envelope): the maximum and / or the minimum of the causal
+ * `grade`-frame window, per channel of an interleaved signal, in one launch:
+ *
+ *   max[f] = max(x[j]),  min[f] = min(x[j])   over  j in [f - grade + 1, f]
+ *
+ * Frames before frame 0.  With d_history (the (grade-1)*channels samples in
+ * front of d_in, as for mavg_run) the window reads them.  With d_history == NULL
+ * the window is TRUNCATED at frame 0: it covers only frames that exist.  This
+ * departs on purpose from the averaging calls' "frames before frame 0 read as
+ * zero": zero is neutral for a sum, not for a maximum, and an all-negative
+ * signal must not report a maximum of 0 during its warm-up.  A caller who wants
+ * zero padding passes a history of zeros.  A chunked streaming caller passes the
+ * previous chunk's last grade - 1 frames as the history and gets exactly the
+ * one-shot output.
+ *
+ * Outputs.  d_max and d_min have the input's dtype and size (int16 -> int16,
+ * fp32 -> fp32); every output is the value of one sample of its window, so the
+ * result is exact for both dtypes.  Either may be NULL, not both; both together
+ * cost one launch and one read of the signal (peak-to-peak, or
+ * peak = max(max, -min)).  The outputs must not overlap d_in or each other.
+ * fp32: +-Inf are ordinary values (an Inf enters the maximum for exactly `grade`
+ * frames, then leaves); -0.0 and +0.0 compare equal and either may be returned;
+ * nothing is promised for NaN input.  grade == 1 is a copy; grade > n_frames is
+ * legal.
+ *
+ * No workspace.  Ownership, stream and capture rules are mavg_run's: no
+ * allocation, no synchronisation, nothing enqueued unless MAVG_OK is returned
+ * (MAVG_ERR_HIP excepted).  n_samples == 0: MAVG_OK, nothing enqueued (the
+ * arguments are validated first).  MAVG_ERR_INVALID_ARG for a bad dtype,
+ * channels < 1, grade < 1, n_samples not a multiple of channels, both outputs
+ * NULL, or a NULL d_in with work to do; MAVG_ERR_MISALIGNED for any view off
+ * sample alignment; MAVG_ERR_UNSUPPORTED past the one-launch limit below.
+ *
+ * Dispatch, evaluated in this order (mavg_extrema_plan shows which):
+ *   extrema_tile   channels 1 or 2, grade >= 2, a halo (grade - 1) * channels *
+ *                  sample size of at most 16 KiB: fp32 grade <= 4097 (mono) /
+ *                  2049 (stereo), int16 grade <= 8193 / 4097.  A tile and its
+ *                  halo are read once; suffix extrema of each 16-B unit and a
+ *                  doubling table over the units' extrema are kept in LDS, so a
+ *                  frame costs a constant number of compares and a unit
+ *                  O(log grade) (DESIGN.md "Extrema").  The 16-B-unit form runs
+ *                  when d_in and every given output are 16-B aligned; other
+ *                  views run the frame-unit form (F=1 in the plan text) over the
+ *                  whole signal.  8 B/sample of traffic for fp32 and 4 for int16
+ *                  with one output; a second output adds its own bytes.
+ *   extrema_strip  everything else (grade == 1, three or more channels, longer
+ *                  halos): one thread per channel of a strip of L frames
+ *                  (L = clamp(grade / 4, 16, 2048), in the plan text) walks back
+ *                  over the grade - 1 frames before its strip, then forward --
+ *                  correct, not fast (about grade / L + 2 reads per output).
+ *
+ * Supported maximum.  One launch of at most 2^32 - 1 work-items: extrema_tile
+ * runs `block` threads per `tile_frames` frames (both in the plan text; the
+ * frame-unit form, 4 frames per thread, refuses from 2^34 frames), extrema_strip
+ * one thread per L frames and channel; past it MAVG_ERR_UNSUPPORTED and nothing
+ * is enqueued.  Frame and sample indices are 64-bit; NOT tested past 2^31 samples.
+ */
+int mavg_extrema_run(const void* d_in, void* d_max /* or NULL */, void* d_min /* or NULL */,
+                     size_t n_samples, int channels, int grade, int dtype,
+                     const void* d_history, void* stream);
+
+/* Describe, without launching anything, what mavg_extrema_run would do:
+ * "extrema_tile<dtype,C=..,F=..,U=..,M=1|2|3,..> max=0|1 min=0|1 ... tile_frames=N ..."
+ * or "extrema_strip dtype=... L=... strips=...".  with_max / with_min: 0 = that
+ * output is NULL (not both), 1 = given; 2 added to either describes views off
+ * 16-B alignment (the frame-unit form).  n_samples == 0 has no plan:
+ * MAVG_ERR_INVALID_ARG. */
+int mavg_extrema_plan(size_t n_samples, int channels, int grade, int dtype,
+                      int with_max, int with_min, char* buf, size_t buflen);
+
 /* Describe, without launching anything, the kernel and launch geometry
  * mavg_run would use for these arguments on 16-B-aligned views
  * (e.g. "tile_scan<f32,...> grid=... block=256 ..."). */

@@ -59,6 +59,16 @@ int mavg_debug_force_cascade(int path);
  * (nothing changes). */
 int mavg_debug_force_stat(int path);
 
+/* TEST HOOK (parity tests and tools/bench_extrema.py): force mavg_extrema_run's
+ * path -- 0: the dispatch rule decides (the default), 1: extrema_tile,
+ * 2: extrema_strip -- so that both paths can run on one shape.  A forced
+ * extrema_tile that cannot take the shape (three or more channels, grade == 1,
+ * a halo past 16 KiB) makes mavg_extrema_run and mavg_extrema_plan return
+ * MAVG_ERR_UNSUPPORTED; the strip takes every shape.  Process-wide, like the
+ * schedule hook; returns MAVG_OK, or MAVG_ERR_INVALID_ARG for another value
+ * (nothing changes). */
+int mavg_debug_force_extrema(int path);
+
 #ifdef __cplusplus
 }
 #endif
