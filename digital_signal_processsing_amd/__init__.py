@@ -12,6 +12,7 @@ only for device memory and streams.
     y = moving_average_decimated(x, grade=400, hop=160)  # only every hop-th output frame, in one launch
     y = moving_rms(x, grade=1024)                      # fp32 RMS / variance / std of the window, one launch
     lo, hi = moving_minmax(x, grade=1024)              # the window's minimum and maximum (peak envelope), one launch
+    y = exponential_moving_average(x, alpha=0.05)      # y[f] = (1-a) y[f-1] + a x[f], fp32 (or span= / halflife= / tau=)
 
 Semantics: ``basics/profilable_moving_averager.cpp:14-37`` -- interleaved
 frames, window ``grade`` frames, zero history (or ``history``: the
@@ -59,6 +60,12 @@ __all__ = [
     "moving_minmax",
     "moving_extrema_into",
     "extrema_plan",
+    "exponential_moving_average",
+    "exponential_moving_average_into",
+    "ema_alpha",
+    "ema_plan",
+    "ema_workspace_bytes",
+    "ema_halo_frames",
     "fill_synthetic",
     "workspace_bytes",
     "resolve_algo",
@@ -817,6 +824,142 @@ def moving_minmax(x, grade: int, channels: int = 1, history=None, stream=None, l
     """``(min, max)`` of the causal ``grade``-frame window from one launch and one read of ``x``
     (peak-to-peak is ``max - min``; the absolute peak ``maximum(max, -min)``)."""
     return _moving_extrema(x, grade, channels, history, stream, library, True, True)
+
+
+def ema_alpha(alpha=None, span=None, halflife=None, tau=None) -> float:
+    """The EMA coefficient from exactly one of ``alpha``, ``span`` (``2 / (span + 1)``),
+    ``halflife`` (``1 - 2**(-1/halflife)``) or ``tau`` (``1 - exp(-1/tau)``), the last three in
+    frames."""
+    import math
+    given = [(n, v) for n, v in (("alpha", alpha), ("span", span), ("halflife", halflife), ("tau", tau)) if v is not None]
+    if len(given) != 1:
+        raise ValueError("exactly one of alpha, span, halflife and tau must be given, got "
+                         + (", ".join(n for n, _ in given) or "none"))
+    name, v = given[0]
+    v = float(v)
+    if name == "alpha":
+        a = v
+    elif name == "span":
+        if not v >= 1:
+            raise ValueError(f"span must be >= 1, got {v}")
+        a = 2.0 / (v + 1.0)
+    else:
+        if not v > 0:
+            raise ValueError(f"{name} must be > 0, got {v}")
+        a = -math.expm1(-math.log(2.0) / v) if name == "halflife" else -math.expm1(-1.0 / v)
+    if not (math.isfinite(a) and 0.0 < a <= 1.0):
+        raise ValueError(f"the coefficient must lie in (0, 1], got {a} from {name}={v}")
+    return a
+
+
+def ema_halo_frames(alpha: float, library: Optional[str] = None) -> int:
+    """``H``: the smallest ``H >= 0`` with ``(1 - alpha)**H <= 2**-30`` -- how far back ``ema_tile``
+    reads to rebuild a tile's carry."""
+    import ctypes
+    out = ctypes.c_longlong(0)
+    _lib.check(_lib.load(library).mavg_ema_halo_frames(alpha, ctypes.byref(out)), "mavg_ema_halo_frames")
+    return out.value
+
+
+def ema_workspace_bytes(n: int, alpha: float, channels: int = 1, dtype: int = F32, library: Optional[str] = None) -> int:
+    """Device workspace ``exponential_moving_average_into`` needs: 0 for ``ema_tile``, one fp64
+    record per 1024-frame tile (``ema_chain``) or per strip (``ema_strip``) and channel."""
+    import ctypes
+    out = ctypes.c_size_t(0)
+    _lib.check(_lib.load(library).mavg_ema_workspace_bytes(n, channels, alpha, dtype, ctypes.byref(out)),
+               "mavg_ema_workspace_bytes")
+    return out.value
+
+
+def ema_plan(n: int, alpha: float, channels: int = 1, dtype: int = F32, state: bool = False, return_state: bool = False,
+             library: Optional[str] = None, aligned: bool = True) -> str:
+    """What mavg_ema_run would do (nothing is launched): ``ema_tile<...> ... halo_frames=H ...
+    tile_frames=N ...``, ``ema_chain<...> ... records=R carry_chunk=K launches=3`` or ``ema_strip
+    ... L=...``.  ``aligned=False``: for views off 16-B alignment (the frame-unit form, ``F=1``)."""
+    import ctypes
+    buf = ctypes.create_string_buffer(512)
+    flags = (1 if state else 0) | (2 if return_state else 0) | (0 if aligned else 4)
+    _lib.check(_lib.load(library).mavg_ema_plan(n, channels, alpha, dtype, flags, buf, len(buf)), "mavg_ema_plan")
+    return buf.value.decode()
+
+
+def _ema_state_ptr(state, C: int, what: str):
+    torch = _torch()
+    if state is None:
+        return None
+    if state.dtype != torch.float64:
+        raise ValueError(f"{what} must be float64 (the carry is kept in fp64), got {state.dtype}")
+    if state.numel() != C:
+        raise ValueError(f"{what} must hold channels = {C} values, got {state.numel()}")
+    if not state.is_cuda or not state.is_contiguous():
+        raise ValueError(f"{what} must be a contiguous device tensor")
+    return state.data_ptr()
+
+
+def exponential_moving_average_into(x, out, alpha=None, *, span=None, halflife=None, tau=None, channels: int = 1,
+                                    state=None, state_out=None, stream=None, workspace=None,
+                                    library: Optional[str] = None) -> None:
+    """Enqueue ``out = exponential_moving_average(x)`` on ``stream`` (default: current).
+
+    ``out``: a contiguous ``float32`` device tensor of ``x``'s size that does not overlap ``x``.
+    ``state`` / ``state_out``: ``float64`` device tensors of ``channels`` values -- ``y[-1]``, and
+    where ``y[last frame]`` goes; not the same tensor.  ``workspace``: as in
+    ``moving_average_rows_into``; ``ema_chain`` and ``ema_strip`` need one (``ema_workspace_bytes``)."""
+    torch = _torch()
+    a = ema_alpha(alpha, span, halflife, tau)
+    frames, C = _decim_shape(x, channels)
+    dt = _dtype_code(x)
+    if out.dtype != torch.float32:
+        raise ValueError(f"out must be float32 (the EMA is fp32 for every input dtype), got {out.dtype}")
+    if out.numel() != x.numel():
+        raise ValueError(f"out must hold x's {x.numel()} samples, got {out.numel()}")
+    for t, what in ((state, "state"), (state_out, "state_out")):
+        if t is not None and (t.dtype != torch.float64 or t.numel() != C):
+            raise ValueError(f"{what} must be a float64 tensor of channels = {C} values, got {t.dtype} x {t.numel()}")
+    _check_device_pair(x, out)
+    sin = _ema_state_ptr(state, C, "state")
+    sout = _ema_state_ptr(state_out, C, "state_out")
+    if sin is not None and sin == sout:
+        raise ValueError("state and state_out must not be the same tensor")
+    ws_n = ema_workspace_bytes(x.numel(), a, C, dt, library)
+    ws, ws_n = _loop_workspace(ws_n, workspace, stream, x.device, "ema_workspace_bytes")
+    st = _lib.load(library).mavg_ema_run(x.data_ptr(), out.data_ptr(), x.numel(), C, a, dt, sin, sout,
+                                         ws.data_ptr() if ws is not None else None, ws_n,
+                                         _stream_handle(stream, x.device))
+    _lib.check(st, "mavg_ema_run")
+
+
+def exponential_moving_average(x, alpha=None, *, span=None, halflife=None, tau=None, channels: int = 1, state=None,
+                               return_state: bool = False, stream=None, workspace=None,
+                               library: Optional[str] = None):
+    """``y[f] = (1 - alpha) y[f-1] + alpha x[f]`` per channel of ``x`` (fp32 or int16), as
+    ``float32`` in ``x``'s shape: ``ewm(adjust=False).mean()``, a one-pole low-pass.  Exactly one of
+    ``alpha``, ``span``, ``halflife`` and ``tau``.  ``state``: ``y[-1]`` as a ``float64`` device
+    tensor of ``channels`` values (default zeros; pass ``x[0]`` for the ``y[-1] = x[0]``
+    convention).  ``return_state``: return ``(y, state)`` with ``y[last frame]`` in fp64 -- the
+    next chunk's ``state``; chunked calls reproduce the one-shot output to the accuracy bar of
+    include/mavg.h, not bitwise."""
+    torch = _torch()
+    ema_alpha(alpha, span, halflife, tau)
+    _check_device_x(x)
+    _decim_shape(x, channels)
+    _dtype_code(x)
+    C = channels if x.dim() == 1 else x.shape[1]
+    _ema_state_ptr(state, C, "state")
+    like = x.new_empty(0, dtype=torch.float32)  # _with_out's model: x's device, float32
+    sout = []
+
+    def into(out):
+        if return_state:
+            sout.append(_on_stream(stream, lambda: torch.zeros(C, dtype=torch.float64, device=x.device)))
+        exponential_moving_average_into(x, out, alpha, span=span, halflife=halflife, tau=tau, channels=C, state=state,
+                                        state_out=sout[0] if sout else None, stream=stream, workspace=workspace,
+                                        library=library)
+
+    out = _with_out(like, stream, into, (x, state), tuple(x.shape))
+    if return_state and x.numel() == 0 and state is not None:
+        sout[0].copy_(state)
+    return (out, sout[0]) if return_state else out
 
 
 def fill_synthetic(n: int, dtype=None, seed: int = 0x5EED, offset: int = 0, dist: int = 0,

@@ -70,6 +70,10 @@ EXPORTED_SYMBOLS = (
     "mavg_stat_plan",
     "mavg_extrema_run",
     "mavg_extrema_plan",
+    "mavg_ema_run",
+    "mavg_ema_workspace_bytes",
+    "mavg_ema_halo_frames",
+    "mavg_ema_plan",
     "mavg_resolve_algo",
     "mavg_plan",
     "mavg_fill_synthetic",
@@ -81,7 +85,7 @@ EXPORTED_SYMBOLS = (
 )
 # exported by the debug build only (include/mavg_debug.h)
 DEBUG_SYMBOLS = ("mavg_test_ahead_schedule", "mavg_debug_force_decim", "mavg_debug_force_cascade",
-                 "mavg_debug_force_stat", "mavg_debug_force_extrema")
+                 "mavg_debug_force_stat", "mavg_debug_force_extrema", "mavg_debug_force_ema")
 # mavg_debug_force_decim's paths (include/mavg_debug.h)
 DECIM_AUTO, DECIM_SCAN, DECIM_WINDOW, DECIM_FULL = 0, 1, 2, 3
 # mavg_debug_force_cascade's paths (include/mavg_debug.h)
@@ -93,6 +97,8 @@ STATS = {"meansq": STAT_MEANSQ, "rms": STAT_RMS, "var": STAT_VAR, "std": STAT_ST
 STAT_AUTO, STAT_TILE, STAT_STRIP = 0, 1, 2
 # mavg_debug_force_extrema's paths (include/mavg_debug.h)
 EXTREMA_AUTO, EXTREMA_TILE, EXTREMA_STRIP = 0, 1, 2
+# mavg_debug_force_ema's paths (include/mavg_debug.h)
+EMA_AUTO, EMA_TILE, EMA_CHAIN, EMA_STRIP = 0, 1, 2, 3
 ABI_VERSION = 4
 DEBUG_LIB_PATH = os.path.join(_PKG, "lib", "libmavg_debug.so")
 # release flags + the test hooks (the forced-schedule parity tests time nothing, but they run the
@@ -181,6 +187,18 @@ def load(path: str = None) -> ctypes.CDLL:
     if hasattr(lib, "mavg_debug_force_extrema"):  # debug and hooks builds only
         lib.mavg_debug_force_extrema.argtypes = [i]
         lib.mavg_debug_force_extrema.restype = i
+    f64 = ctypes.c_double
+    lib.mavg_ema_run.argtypes = [vp, vp, sz, i, f64, i, vp, vp, vp, sz, vp]
+    lib.mavg_ema_run.restype = i
+    lib.mavg_ema_workspace_bytes.argtypes = [sz, i, f64, i, ctypes.POINTER(sz)]
+    lib.mavg_ema_workspace_bytes.restype = i
+    lib.mavg_ema_halo_frames.argtypes = [f64, ctypes.POINTER(ctypes.c_longlong)]
+    lib.mavg_ema_halo_frames.restype = i
+    lib.mavg_ema_plan.argtypes = [sz, i, f64, i, i, ctypes.c_char_p, sz]
+    lib.mavg_ema_plan.restype = i
+    if hasattr(lib, "mavg_debug_force_ema"):  # debug and hooks builds only
+        lib.mavg_debug_force_ema.argtypes = [i]
+        lib.mavg_debug_force_ema.restype = i
     lib.mavg_resolve_algo.argtypes = [sz, i, i, i, i]
     lib.mavg_resolve_algo.restype = i
     lib.mavg_plan.argtypes = [sz, i, i, i, i, i, ctypes.c_char_p, sz]

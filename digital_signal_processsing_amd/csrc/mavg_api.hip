@@ -573,6 +573,60 @@ int extrema_launch(int path, const ExtremaCall& a, hipStream_t s) {
   return extrema_tile_any(a.dtype, a.C, es, a.k, s);
 }
 
+// ---- exponential moving average (mavg_ema_run) -----------------------------------------------
+int validate_ema(size_t n, int C, double alpha, int dtype) {
+  const int st = validate(n, C, 1, dtype, MAVG_ALGO_AUTO, 0);
+  if (st != MAVG_OK) return st;
+  // (below 2^-52, 1 - alpha is 1 in fp64: the filter would never forget)
+  if (!std::isfinite(alpha) || !(alpha > 0.0) || alpha > 1.0 || alpha < 0x1p-52) return MAVG_ERR_INVALID_ARG;
+  return MAVG_OK;
+}
+
+// The dispatch rule, in the order mavg.h gives; *path = kEmaTile / kEmaChain / kEmaStrip.  The test
+// hook's forced path replaces the rule: MAVG_ERR_UNSUPPORTED where the forced kernel cannot take
+// the shape (a tile past the stage limit, a tile or chain with three or more channels).
+int ema_path(int C, double alpha, int dtype, int* path) {
+  const bool tile_ok = ema_tile_fits(dtype, C, alpha);
+  const bool chain_ok = C <= 2;
+  int forced = kEmaAuto;
+#ifdef MAVG_TEST_HOOKS
+  forced = g_test_ema_path.load(std::memory_order_relaxed);
+#endif
+  if ((forced == kEmaTile && !tile_ok) || (forced == kEmaChain && !chain_ok)) return MAVG_ERR_UNSUPPORTED;
+  *path = forced != kEmaAuto ? forced : tile_ok ? kEmaTile : chain_ok ? kEmaChain : kEmaStrip;
+  return MAVG_OK;
+}
+
+struct EmaCall {
+  const void* in;
+  float* out;
+  const double* state_in;
+  double* state_out;
+  size_t n;
+  int C;
+  double alpha;
+  int dtype;
+};
+
+// what mavg_ema_workspace_bytes returns for a path
+int ema_ws_bytes(int path, const EmaCall& a, size_t* bytes) {
+  *bytes = 0;
+  if (path == kEmaTile) return MAVG_OK;
+  const size_t nframes = a.n / (size_t)a.C;
+  return path == kEmaChain ? ema_chain_ws_bytes(nframes, a.C, bytes) : ema_strip_ws_bytes(nframes, a.C, bytes);
+}
+
+// The launches of one path (plan mode when g_plan is set); views of any sample alignment: the
+// 16-B-unit form when d_in and d_out are 16-B aligned, else the frame-unit form over the whole
+// signal (no head is peeled).
+int ema_launch(int path, const EmaCall& a, Workspace ws, hipStream_t s) {
+  EmaSig es{a.in, a.out, a.state_in, a.state_out, a.n / (size_t)a.C, a.alpha};
+  if (path == kEmaStrip) return ema_strip_any(a.dtype, a.C, es, ws, s);
+  es.unit = aligned(a.in, 16) && aligned(a.out, 16);
+  es.eio = !es.unit && !aligned(a.in, elem_size(a.dtype) * (size_t)a.C) ? 1 : 0;
+  return path == kEmaTile ? ema_tile_any(a.dtype, a.C, es, s) : ema_chain_any(a.dtype, a.C, es, ws, s);
+}
+
 // cascade_loop's workspace, in this order: the ping-pong buffer (the signal's bytes, 16-B padded);
 // with a history two block buffers of passes * (grade - 1) * C samples each (16-B padded); then
 // mavg_run's own workspace -- the signal's, and with a history at least the first block's.
@@ -1046,6 +1100,82 @@ int mavg_extrema_run(const void* d_in, void* d_max, void* d_min, size_t n_sample
   if (st != MAVG_OK) return st;
   return extrema_launch(path, ExtremaCall{d_in, d_max, d_min, d_history, n_samples, channels, grade, dtype},
                         static_cast<hipStream_t>(stream));
+}
+
+int mavg_ema_halo_frames(double alpha, long long* out_frames) {
+  if (out_frames == nullptr) return MAVG_ERR_INVALID_ARG;
+  const int st = validate_ema(0, 1, alpha, MAVG_F32);
+  if (st != MAVG_OK) return st;
+  *out_frames = ema_halo_frames(alpha);
+  return MAVG_OK;
+}
+
+int mavg_ema_workspace_bytes(size_t n_samples, int channels, double alpha, int dtype, size_t* out_bytes) {
+  if (out_bytes == nullptr) return MAVG_ERR_INVALID_ARG;
+  int st = validate_ema(n_samples, channels, alpha, dtype);
+  if (st != MAVG_OK) return st;
+  *out_bytes = 0;
+  if (n_samples == 0) return MAVG_OK;
+  int path = kEmaStrip;
+  st = ema_path(channels, alpha, dtype, &path);
+  if (st != MAVG_OK) return st;
+  const EmaCall a{kPlanIn, static_cast<float*>(kPlanOut), nullptr, nullptr, n_samples, channels, alpha, dtype};
+  {
+    // the launches' own limit (grid_too_large) shows here as it does in mavg_ema_run
+    PlanScope ps;
+    st = ema_launch(path, a, Workspace{}, nullptr);
+    if (st != MAVG_OK) return st;
+  }
+  return ema_ws_bytes(path, a, out_bytes);
+}
+
+int mavg_ema_plan(size_t n_samples, int channels, double alpha, int dtype, int flags, char* buf, size_t buflen) {
+  if (buf == nullptr || buflen == 0) return MAVG_ERR_INVALID_ARG;
+  buf[0] = 0;
+  int st = validate_ema(n_samples, channels, alpha, dtype);
+  if (st != MAVG_OK) return st;
+  if (flags < 0 || flags > 7) return MAVG_ERR_INVALID_ARG;
+  if (n_samples == 0) return MAVG_ERR_INVALID_ARG;  // nothing to describe, as mavg_plan
+  int path = kEmaStrip;
+  st = ema_path(channels, alpha, dtype, &path);
+  if (st != MAVG_OK) return st;
+  PlanScope ps;
+  // (flag 4: views off 16-B alignment -- an input one sample past a 16-B boundary)
+  const void* const in = (flags & 4) != 0 ? static_cast<const char*>(kPlanIn) + elem_size(dtype) : kPlanIn;
+  const double* const sin = (flags & 1) != 0 ? static_cast<const double*>(kPlanOff) : nullptr;
+  double* const sout = (flags & 2) != 0 ? static_cast<double*>(const_cast<void*>(kPlanOff)) + 64 : nullptr;
+  st = ema_launch(path, EmaCall{in, static_cast<float*>(kPlanOut), sin, sout, n_samples, channels, alpha, dtype},
+                  Workspace{}, nullptr);
+  if (st == MAVG_OK) snprintf(buf, buflen, "%s", ps.plan.text);
+  return st;
+}
+
+// One launch of the tile kernel where the rule (ema_path) takes the coefficient, else the three
+// launches of the chain or the strip form, all planned before the first is made.
+int mavg_ema_run(const void* d_in, float* d_out, size_t n_samples, int channels, double alpha, int dtype,
+                 const double* d_state_in, double* d_state_out, void* d_ws, size_t ws_bytes, void* stream) {
+  int st = validate_ema(n_samples, channels, alpha, dtype);
+  if (st != MAVG_OK) return st;
+  if (d_state_in != nullptr && d_state_in == d_state_out) return MAVG_ERR_INVALID_ARG;
+  if (n_samples == 0) return MAVG_OK;
+  if (d_in == nullptr || d_out == nullptr) return MAVG_ERR_INVALID_ARG;
+  if (!aligned(d_in, elem_size(dtype)) || !aligned(d_out, 4) || !aligned(d_state_in, 8) || !aligned(d_state_out, 8))
+    return MAVG_ERR_MISALIGNED;
+  int path = kEmaStrip;
+  st = ema_path(channels, alpha, dtype, &path);
+  if (st != MAVG_OK) return st;
+  const EmaCall a{d_in, d_out, d_state_in, d_state_out, n_samples, channels, alpha, dtype};
+  {
+    PlanScope ps;  // every launch's limits, with nothing enqueued
+    st = ema_launch(path, a, Workspace{}, nullptr);
+    if (st != MAVG_OK) return st;
+  }
+  size_t need = 0;
+  st = ema_ws_bytes(path, a, &need);
+  if (st != MAVG_OK) return st;
+  st = check_workspace(need, d_ws, ws_bytes);
+  if (st != MAVG_OK) return st;
+  return ema_launch(path, a, Workspace{d_ws, ws_bytes}, static_cast<hipStream_t>(stream));
 }
 
 int mavg_ragged_workspace_bytes(const int64_t* h_offsets, size_t rows, int channels, int grade, int dtype,

@@ -112,6 +112,27 @@ __device__ __forceinline__ A wave_incl_scan(A v) {
   return v;
 }
 
+// Decayed inclusive scan across the 64 lanes (mavg_ema.hpp): lane l ends with
+//     v[l] + q v[l-1] + q^2 v[l-2] + ... + q^l v[0],
+// the composition of 64 steps y_out = q y_in + v of a constant-coefficient recurrence.  The six
+// steps of wave_incl_scan, each add an fma with the power of q that spans the step's distance:
+// q, q^2, q^4, q^8 (wave-uniform) for the row shifts; for the two row broadcasts the distance
+// depends on the lane -- w15 = q^((lane & 15) + 1) from lane 15 of the row before, w31 =
+// q^((lane & 31) + 1) from lane 31 -- and the caller forms both once per kernel from host-computed
+// powers.  Lanes a step does not write receive 0, so their fma leaves v as it is.  The exclusive
+// value of a lane is the inclusive value of the lane before it (a lane shift), never a division
+// by a weight: q may be 0 or underflow.
+__device__ __forceinline__ double wave_decay_scan(double v, double q1, double q2, double q4, double q8, double w15,
+                                                  double w31) {
+  v = fma(q1, dpp<0x111, 0xf, 0xf>(v), v);
+  v = fma(q2, dpp<0x112, 0xf, 0xf>(v), v);
+  v = fma(q4, dpp<0x114, 0xf, 0xf>(v), v);
+  v = fma(q8, dpp<0x118, 0xf, 0xf>(v), v);
+  v = fma(w15, dpp<0x142, 0xa, 0xf>(v), v);
+  v = fma(w31, dpp<0x143, 0xc, 0xf>(v), v);
+  return v;
+}
+
 // N independent inclusive scans, step by step across the N values (each value sees the same
 // six additions in the same order as wave_incl_scan): the DPP moves of one value fill the wait
 // states after the previous value's add instead of s_nops on one dependent chain

@@ -309,6 +309,44 @@ int extrema_tile_any(int dtype, int C, const ExtremaSig& es, int grade, hipStrea
 int extrema_strip_frames(int grade);
 int extrema_strip_any(int dtype, int C, const ExtremaSig& es, int grade, hipStream_t st);
 
+// The exponential moving average (mavg_ema.hpp, instantiated in mavg_ema.hip): y[f] = (1 - alpha)
+// y[f-1] + alpha x[f], fp32 out; state_in / state_out: `C` doubles in device memory or NULL.
+//   unit  the 16-B-unit form (in and out 16-B aligned); else the frame-unit (F = 1) form
+//   eio   frame-unit form on an input that is only element-aligned (UnitIO::gload)
+struct EmaSig {
+  const void* in;
+  float* out;
+  const double* state_in;
+  double* state_out;
+  size_t nframes;
+  double alpha;
+  bool unit = true;
+  int eio = 0;
+};
+// The test hook's forced path (mavg_debug_force_ema, include/mavg_debug.h): 0 = the rule decides
+constexpr int kEmaAuto = 0, kEmaTile = 1, kEmaChain = 2, kEmaStrip = 3;
+#ifdef MAVG_TEST_HOOKS
+extern std::atomic<int> g_test_ema_path;
+#endif
+// H: the smallest H >= 0 with (1 - alpha)^H <= 2^-30 (0 for alpha == 1); alpha validated
+long long ema_halo_frames(double alpha);
+// Whether the one-launch tile kernel takes this coefficient (the dispatch rule, and what a forced
+// ema_tile may run): channels 1 or 2, a halo H * C * sample size of at most 16 KiB, and its LDS
+// layout (EmaLds) inside lds_budget in both forms.
+bool ema_tile_fits(int dtype, int C, double alpha);
+// MAVG_ERR_UNSUPPORTED: the halo does not fit, or the launch would exceed grid_too_large
+int ema_tile_any(int dtype, int C, const EmaSig& es, hipStream_t st);
+// The chain (channels 1 or 2, else MAVG_ERR_UNSUPPORTED) and the strip form (every channel count):
+// three launches through one fp64 record per tile or strip and channel; every launch is checked
+// before the first is made.  MAVG_ERR_WORKSPACE / MAVG_ERR_MISALIGNED for the workspace.
+int ema_chain_any(int dtype, int C, const EmaSig& es, Workspace ws, hipStream_t st);
+int ema_strip_any(int dtype, int C, const EmaSig& es, Workspace ws, hipStream_t st);
+// What mavg_ema_workspace_bytes returns for the two: the records of the smaller (frame-unit) tile,
+// so that a misaligned view fits, or of the strips, times C * 8, rounded up to 16.
+// MAVG_ERR_UNSUPPORTED where the byte count leaves size_t.
+int ema_chain_ws_bytes(size_t nframes, int C, size_t* bytes);
+int ema_strip_ws_bytes(size_t nframes, int C, size_t* bytes);
+
 // ceil(k / F): the units a k-frame halo takes (TileParams / AheadParams halo_units)
 template <int F>
 constexpr size_t tile_halo_units(int k) { return (size_t)(((long long)k + F - 1) / F); }

@@ -591,6 +591,114 @@ int mavg_extrema_run(const void* d_in, void* d_max /* or NULL */, void* d_min /*
 int mavg_extrema_plan(size_t n_samples, int channels, int grade, int dtype,
                       int with_max, int with_min, char* buf, size_t buflen);
 
+/* Exponential moving average (EMA, one-pole low-pass, leaky integrator), per
+ * channel of an interleaved signal x[f*C + c]:
+ *
+ *   y[f] = (1 - alpha) y[f-1] + alpha x[f],     0 < alpha <= 1
+ *
+ * -- ewm(adjust=False).mean(), the smoother behind envelope followers, the
+ * running mean of an online normaliser.  The first filter here with infinite
+ * memory: every output depends on every earlier frame.
+ *
+ * dtype is MAVG_F32 or MAVG_I16.  The output is ALWAYS fp32, for int16 input too
+ * (n_samples floats, in d_in's layout); it must not overlap d_in.
+ *
+ * State.  y[-1] is 0 per channel when d_state_in is NULL (frames before the
+ * first read as zero); otherwise y[-1] = d_state_in[c], `channels` doubles in
+ * device memory, 8-B aligned.  A caller who wants the y[-1] = x[0] convention
+ * passes x[0] as the state.  d_state_out (`channels` doubles, 8-B aligned, or
+ * NULL) receives y[last frame] per channel in fp64 from the same call.  The two
+ * state pointers must not be equal (MAVG_ERR_INVALID_ARG: the tile kernel's
+ * first tiles read one while its last tile writes the other).  Passing chunk
+ * i's state_out as chunk i+1's state_in reproduces the one-shot output within
+ * the accuracy bar below -- NOT bitwise: the association of the fp64 sums
+ * depends on the tiling.
+ *
+ * Accuracy.  Everything is evaluated in fp64 and rounded once to fp32.  With
+ * y_ref the fp64 serial recurrence and M the largest of |x| over the signal and
+ * |state_in|, every output satisfies
+ *
+ *   |y - y_ref| <= 2^-23 |y_ref| + 2^-29 M
+ *
+ * (the fp32 rounding, doubled; the truncation of ema_tile, at most 2^-30 M, and
+ * fp64 re-association).  ema_chain and ema_strip do not truncate: their
+ * d_state_out is within 1e-12 M of the reference; ema_tile's within 2^-29 M.
+ * Nothing is promised for non-finite fp32 input.
+ *
+ * Ownership, stream and capture rules are mavg_run's: no allocation, no
+ * synchronisation, every step planned before the first is launched, nothing
+ * enqueued unless MAVG_OK is returned (MAVG_ERR_HIP excepted).  The workspace
+ * needs no initialisation -- every record read is written earlier in the same
+ * call -- so a call may be captured into a graph with no memset node.
+ * n_samples == 0: MAVG_OK, nothing enqueued, d_state_out untouched.
+ *
+ * Status: MAVG_ERR_INVALID_ARG for a bad dtype, channels < 1, n_samples not a
+ * multiple of channels, alpha not finite, <= 0, > 1 or below 2^-52 (1 - alpha is
+ * then 1 in fp64), equal state pointers, or a NULL view with work to do;
+ * MAVG_ERR_MISALIGNED for d_in off sample alignment, d_out off 4 B, a state
+ * pointer off 8 B or d_ws off 16 B; MAVG_ERR_WORKSPACE for ws_bytes too small;
+ * MAVG_ERR_UNSUPPORTED past the one-launch limit below.
+ *
+ * Dispatch, evaluated in this order (mavg_ema_plan shows which).  With d = 1 -
+ * alpha, the recurrence over m frames composes to y_out = d^m y_in + b, so only
+ * b is scanned and every multiplier is a power of d computed on the host; and
+ * the memory decays: H = mavg_ema_halo_frames(alpha) frames back a sample weighs
+ * at most 2^-30 of its value.
+ *   ema_tile   channels 1 or 2 and a halo H * channels * sample size of at most
+ *              16 KiB (the stage limit of every tile kernel here; measured 1.1x
+ *              to 2.3x faster than the forced chain over that whole range,
+ *              DESIGN.md "EMA").  One launch, no workspace.  A tile
+ *              stages its H halo frames in front of its own and rebuilds its
+ *              carry-in from them; tiles within H frames of the start add the
+ *              state in closed form.  alpha == 1 (H = 0) is the converting copy.
+ *              The 16-B-unit form runs when d_in and d_out are 16-B aligned;
+ *              other views run the frame-unit form (F=1 in the plan text) over
+ *              the whole signal.  8 B/sample of traffic for fp32, 6 for int16.
+ *   ema_chain  channels 1 or 2, any alpha: three launches through one fp64
+ *              record per tile and channel -- the tiles' aggregates, one
+ *              workgroup that turns them in place into the tiles' carry-ins
+ *              (and writes d_state_out), the tiles again from their carry-ins.
+ *              No truncation.  12 B/sample for fp32 (x is read twice), 8 for
+ *              int16, plus 16 B per tile.
+ *   ema_strip  three or more channels: the same three steps with one thread per
+ *              strip of L frames and channel at both ends (L in the plan text)
+ *              -- correct, not fast.
+ *
+ * Workspace (mavg_ema_workspace_bytes): 0 for ema_tile; for ema_chain the record
+ * count of the smaller tile of the frame-unit form (1024 frames), so that a
+ * misaligned view fits, times channels * 8, rounded up to 16; for ema_strip the
+ * strip count times channels * 8, rounded up to 16.  d_ws 16-B aligned.
+ *
+ * Supported maximum.  Each launch takes at most 2^32 - 1 work-items: the tile
+ * kernels run `block` threads per `tile_frames` frames (both in the plan text;
+ * the frame-unit form, 4 frames per thread, refuses from 2^34 frames), the
+ * strip kernels one thread per L frames and channel; past it
+ * MAVG_ERR_UNSUPPORTED and nothing is enqueued.  Frame and sample indices are
+ * 64-bit wherever they are not tile-local; NOT tested past 2^31 samples.
+ */
+int mavg_ema_run(const void* d_in, float* d_out, size_t n_samples, int channels,
+                 double alpha, int dtype,
+                 const double* d_state_in /* or NULL */, double* d_state_out /* or NULL */,
+                 void* d_ws, size_t ws_bytes, void* stream);
+
+/* Device workspace mavg_ema_run needs for these arguments (see "Workspace"
+ * above); the argument checks and the one-launch limit are mavg_ema_run's. */
+int mavg_ema_workspace_bytes(size_t n_samples, int channels, double alpha, int dtype,
+                             size_t* out_bytes);
+
+/* H: the smallest H >= 0 with (1 - alpha)^H <= 2^-30 -- 0 for alpha == 1, 30 for
+ * alpha == 0.5, about 20.8 / alpha for small alpha. */
+int mavg_ema_halo_frames(double alpha, long long* out_frames);
+
+/* Describe, without launching anything, what mavg_ema_run would do:
+ * "ema_tile<dtype,C=..,F=..,U=..,nt=..> alpha=.. halo_frames=H state=0|1|2|3 ... tile_frames=N ...",
+ * "ema_chain<...> ... tile_frames=N records=R carry_chunk=K launches=3" or
+ * "ema_strip dtype=.. C=.. L=.. strips=.. carry_chunk=K launches=3 ...".
+ * flags: 1 = a d_state_in, 2 = a d_state_out, 4 = views off 16-B alignment (the
+ * frame-unit form).  n_samples == 0 has no plan: MAVG_ERR_INVALID_ARG. */
+int mavg_ema_plan(size_t n_samples, int channels, double alpha, int dtype, int flags,
+                  char* buf, size_t buflen);
+
 /* Describe, without launching anything, the kernel and launch geometry
  * mavg_run would use for these arguments on 16-B-aligned views
  * (e.g. "tile_scan<f32,...> grid=... block=256 ..."). */

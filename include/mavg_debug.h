@@ -69,6 +69,17 @@ int mavg_debug_force_stat(int path);
  * (nothing changes). */
 int mavg_debug_force_extrema(int path);
 
+/* TEST HOOK (parity tests and tools/bench_ema.py): force mavg_ema_run's path --
+ * 0: the dispatch rule decides (the default), 1: ema_tile, 2: ema_chain,
+ * 3: ema_strip -- so that the paths can run on one shape.  A forced path that
+ * cannot take the shape (ema_tile past its 16-KiB halo limit, ema_tile or
+ * ema_chain with three or more channels) makes mavg_ema_run, mavg_ema_plan and
+ * mavg_ema_workspace_bytes return MAVG_ERR_UNSUPPORTED; the workspace query
+ * follows the forced path; the strip takes every shape.  Process-wide, like the
+ * schedule hook; returns MAVG_OK, or MAVG_ERR_INVALID_ARG for another value
+ * (nothing changes). */
+int mavg_debug_force_ema(int path);
+
 #ifdef __cplusplus
 }
 #endif
