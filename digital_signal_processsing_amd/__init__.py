@@ -66,6 +66,12 @@ __all__ = [
     "ema_plan",
     "ema_workspace_bytes",
     "ema_halo_frames",
+    "biquad",
+    "biquad_into",
+    "biquad_plan",
+    "biquad_workspace_bytes",
+    "biquad_halo_frames",
+    "sos_filter",
     "fill_synthetic",
     "workspace_bytes",
     "resolve_algo",
@@ -955,6 +961,194 @@ def exponential_moving_average(x, alpha=None, *, span=None, halflife=None, tau=N
         exponential_moving_average_into(x, out, alpha, span=span, halflife=halflife, tau=tau, channels=C, state=state,
                                         state_out=sout[0] if sout else None, stream=stream, workspace=workspace,
                                         library=library)
+
+    out = _with_out(like, stream, into, (x, state), tuple(x.shape))
+    if return_state and x.numel() == 0 and state is not None:
+        sout[0].copy_(state)
+    return (out, sout[0]) if return_state else out
+
+
+def biquad_coef(coef):
+    """``(b0, b1, b2, a1, a2)`` as five floats from 5 numbers, or from a scipy-style row of 6
+    ``(b0, b1, b2, a0, a1, a2)``, which is divided by ``a0`` (``a0 == 0`` is rejected)."""
+    import math
+    try:
+        c = [float(v) for v in (coef.tolist() if hasattr(coef, "tolist") else coef)]
+    except TypeError:
+        raise ValueError("coef must be 5 numbers (b0 b1 b2 a1 a2) or a row of 6 (b0 b1 b2 a0 a1 a2)") from None
+    if len(c) == 6:
+        a0 = c[3]
+        if a0 == 0.0 or not math.isfinite(a0):
+            raise ValueError(f"a0 must be finite and non-zero, got {a0}")
+        c = [c[0] / a0, c[1] / a0, c[2] / a0, c[4] / a0, c[5] / a0]
+    if len(c) != 5:
+        raise ValueError(f"coef must be 5 numbers (b0 b1 b2 a1 a2) or a row of 6 (b0 b1 b2 a0 a1 a2), got {len(c)}")
+    if not all(math.isfinite(v) for v in c):
+        raise ValueError(f"the coefficients must be finite, got {c}")
+    if not (abs(c[4]) < 1.0 and abs(c[3]) < 1.0 + c[4]):
+        raise ValueError(f"the poles must lie strictly inside the unit circle (|a2| < 1 and |a1| < 1 + a2), got a1={c[3]} a2={c[4]}")
+    return tuple(c)
+
+
+def _coef5(coef):
+    import ctypes
+    return (ctypes.c_double * 5)(*biquad_coef(coef))
+
+
+def biquad_halo_frames(coef, library: Optional[str] = None) -> int:
+    """``H``: a frame count past which the impulse response sums to at most ``2**-30`` of its
+    whole (include/mavg.h "Halo") -- how far back ``biquad_tile`` reads to rebuild a tile's state."""
+    import ctypes
+    out = ctypes.c_longlong(0)
+    _lib.check(_lib.load(library).mavg_biquad_halo_frames(_coef5(coef), ctypes.byref(out)), "mavg_biquad_halo_frames")
+    return out.value
+
+
+def biquad_workspace_bytes(n: int, coef, channels: int = 1, dtype: int = F32, library: Optional[str] = None) -> int:
+    """Device workspace ``biquad_into`` needs: 0 for ``biquad_tile``, two fp64 values per
+    1024-frame tile (``biquad_chain``) or per strip (``biquad_strip``) and channel."""
+    import ctypes
+    out = ctypes.c_size_t(0)
+    _lib.check(_lib.load(library).mavg_biquad_workspace_bytes(n, channels, _coef5(coef), dtype, ctypes.byref(out)),
+               "mavg_biquad_workspace_bytes")
+    return out.value
+
+
+def biquad_plan(n: int, coef, channels: int = 1, dtype: int = F32, state: bool = False, return_state: bool = False,
+                library: Optional[str] = None, aligned: bool = True) -> str:
+    """What mavg_biquad_run would do (nothing is launched): ``biquad_tile<...> halo_frames=H ...
+    tile_frames=N ...``, ``biquad_chain<...> ... records=R carry_chunk=K launches=3`` or
+    ``biquad_strip ... L=...``.  ``aligned=False``: for views off 16-B alignment (``F=1``)."""
+    import ctypes
+    buf = ctypes.create_string_buffer(512)
+    flags = (1 if state else 0) | (2 if return_state else 0) | (0 if aligned else 4)
+    _lib.check(_lib.load(library).mavg_biquad_plan(n, channels, _coef5(coef), dtype, flags, buf, len(buf)),
+               "mavg_biquad_plan")
+    return buf.value.decode()
+
+
+def _biquad_state_shape(state, C: int, what: str) -> None:
+    torch = _torch()
+    if state is None:
+        return
+    if state.dtype != torch.float64:
+        raise ValueError(f"{what} must be float64 (the state is kept in fp64), got {state.dtype}")
+    if state.numel() != 2 * C:
+        raise ValueError(f"{what} must hold channels x 2 = {2 * C} values, got {state.numel()}")
+
+
+def _biquad_state_ptr(state, C: int, what: str):
+    """The state's device pointer (None without one); _biquad_state_shape has seen it."""
+    if state is None:
+        return None
+    if not state.is_cuda or not state.is_contiguous():
+        raise ValueError(f"{what} must be a contiguous device tensor")
+    return state.data_ptr()
+
+
+def biquad_into(x, out, coef, channels: int = 1, state=None, state_out=None, stream=None, workspace=None,
+                library: Optional[str] = None) -> None:
+    """Enqueue ``out = biquad(x)`` on ``stream`` (default: current).
+
+    ``out``: a contiguous ``float32`` device tensor of ``x``'s size that does not overlap ``x``.
+    ``state`` / ``state_out``: ``float64`` device tensors of ``[channels, 2]`` values -- the
+    transposed direct form II's ``s1, s2`` before the first frame, and where those after the last
+    go; not the same tensor.  ``workspace``: as in ``exponential_moving_average_into``;
+    ``biquad_chain`` and ``biquad_strip`` need one (``biquad_workspace_bytes``)."""
+    torch = _torch()
+    c5 = _coef5(coef)
+    frames, C = _decim_shape(x, channels)
+    dt = _dtype_code(x)
+    if out.dtype != torch.float32:
+        raise ValueError(f"out must be float32 (the biquad is fp32 for every input dtype), got {out.dtype}")
+    if out.numel() != x.numel():
+        raise ValueError(f"out must hold x's {x.numel()} samples, got {out.numel()}")
+    _biquad_state_shape(state, C, "state")
+    _biquad_state_shape(state_out, C, "state_out")
+    _check_device_pair(x, out)
+    sin = _biquad_state_ptr(state, C, "state")
+    sout = _biquad_state_ptr(state_out, C, "state_out")
+    if sin is not None and sin == sout:
+        raise ValueError("state and state_out must not be the same tensor")
+    lib = _lib.load(library)
+    ws_n = biquad_workspace_bytes(x.numel(), tuple(c5), C, dt, library)
+    ws, ws_n = _loop_workspace(ws_n, workspace, stream, x.device, "biquad_workspace_bytes")
+    st = lib.mavg_biquad_run(x.data_ptr(), out.data_ptr(), x.numel(), C, c5, dt, sin, sout,
+                             ws.data_ptr() if ws is not None else None, ws_n, _stream_handle(stream, x.device))
+    _lib.check(st, "mavg_biquad_run")
+
+
+def biquad(x, coef, channels: int = 1, state=None, return_state: bool = False, stream=None, workspace=None,
+           library: Optional[str] = None):
+    """``y[f] = b0 x[f] + b1 x[f-1] + b2 x[f-2] - a1 y[f-1] - a2 y[f-2]`` per channel of ``x`` (fp32
+    or int16), as ``float32`` in ``x``'s shape.  ``coef``: ``(b0, b1, b2, a1, a2)`` or a scipy-style
+    row ``(b0, b1, b2, a0, a1, a2)``; the poles must lie strictly inside the unit circle.
+    ``state``: ``scipy.signal.lfilter``'s ``zi`` per channel, a ``float64`` device tensor of
+    ``[channels, 2]`` values (default zeros).  ``return_state``: return ``(y, state)`` with the
+    state after the last frame -- the next chunk's ``state``; chunked calls reproduce the one-shot
+    output to the accuracy bar of include/mavg.h, not bitwise."""
+    torch = _torch()
+    biquad_coef(coef)
+    _check_device_x(x)
+    _decim_shape(x, channels)
+    _dtype_code(x)
+    C = channels if x.dim() == 1 else x.shape[1]
+    _biquad_state_shape(state, C, "state")
+    _biquad_state_ptr(state, C, "state")
+    like = x.new_empty(0, dtype=torch.float32)  # _with_out's model: x's device, float32
+    sout = []
+
+    def into(out):
+        if return_state:
+            sout.append(_on_stream(stream, lambda: torch.zeros((C, 2), dtype=torch.float64, device=x.device)))
+        biquad_into(x, out, coef, channels=C, state=state, state_out=sout[0] if sout else None, stream=stream,
+                    workspace=workspace, library=library)
+
+    out = _with_out(like, stream, into, (x, state), tuple(x.shape))
+    if return_state and x.numel() == 0 and state is not None:
+        sout[0].copy_(state.reshape(C, 2))
+    return (out, sout[0]) if return_state else out
+
+
+def sos_filter(x, sos, channels: int = 1, state=None, return_state: bool = False, stream=None,
+               library: Optional[str] = None):
+    """A cascade of second-order sections (``scipy.signal.sosfilt``): ``sos`` is ``[S, 6]`` rows
+    ``(b0, b1, b2, a0, a1, a2)``, run one ``mavg_biquad_run`` each through two ping-pong fp32
+    buffers -- the first section reads ``x`` in its dtype, the later ones fp32, the last lands in the
+    result.  THE INTERMEDIATE BETWEEN SECTIONS IS fp32 (one rounding per section, about ``2**-24``
+    of the intermediate's size); a cascade that needs an fp64 intermediate is not this function.
+    ``state``: a ``float64`` device tensor ``[S, channels, 2]`` (``sosfilt``'s ``zi`` with the
+    channel axis second); ``return_state``: return ``(y, state)`` of that shape."""
+    torch = _torch()
+    rows = sos.tolist() if hasattr(sos, "tolist") else [list(r) for r in sos]
+    if not rows or any(not hasattr(r, "__len__") or len(r) != 6 for r in rows):
+        raise ValueError("sos must be a non-empty [S, 6] array of (b0, b1, b2, a0, a1, a2) rows")
+    coefs = [biquad_coef(r) for r in rows]
+    S = len(coefs)
+    _check_device_x(x)
+    _decim_shape(x, channels)
+    _dtype_code(x)
+    C = channels if x.dim() == 1 else x.shape[1]
+    if state is not None:
+        if state.dtype != torch.float64 or state.numel() != S * C * 2 or not state.is_cuda or not state.is_contiguous():
+            raise ValueError(f"state must be a contiguous float64 device tensor of [sections, channels, 2] = "
+                             f"[{S}, {C}, 2] values")
+        state = state.reshape(S, C, 2)
+    like = x.new_empty(0, dtype=torch.float32)  # _with_out's model: x's device, float32
+    sout = []
+
+    def into(out):
+        if return_state:
+            sout.append(_on_stream(stream, lambda: torch.zeros((S, C, 2), dtype=torch.float64, device=x.device)))
+        other = _on_stream(stream, lambda: torch.empty_like(out)) if S > 1 else None
+        cur = x
+        for j, c in enumerate(coefs):
+            dst = out if (S - 1 - j) % 2 == 0 else other      # the last section lands in the result
+            biquad_into(cur, dst, c, channels=C, state=state[j] if state is not None else None,
+                        state_out=sout[0][j] if sout else None, stream=stream, library=library)
+            cur = dst
+        if other is not None and stream is not None:
+            other.record_stream(stream)
 
     out = _with_out(like, stream, into, (x, state), tuple(x.shape))
     if return_state and x.numel() == 0 and state is not None:

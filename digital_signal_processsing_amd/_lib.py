@@ -74,6 +74,10 @@ EXPORTED_SYMBOLS = (
     "mavg_ema_workspace_bytes",
     "mavg_ema_halo_frames",
     "mavg_ema_plan",
+    "mavg_biquad_run",
+    "mavg_biquad_workspace_bytes",
+    "mavg_biquad_halo_frames",
+    "mavg_biquad_plan",
     "mavg_resolve_algo",
     "mavg_plan",
     "mavg_fill_synthetic",
@@ -85,7 +89,8 @@ EXPORTED_SYMBOLS = (
 )
 # exported by the debug build only (include/mavg_debug.h)
 DEBUG_SYMBOLS = ("mavg_test_ahead_schedule", "mavg_debug_force_decim", "mavg_debug_force_cascade",
-                 "mavg_debug_force_stat", "mavg_debug_force_extrema", "mavg_debug_force_ema")
+                 "mavg_debug_force_stat", "mavg_debug_force_extrema", "mavg_debug_force_ema",
+                 "mavg_debug_force_biquad")
 # mavg_debug_force_decim's paths (include/mavg_debug.h)
 DECIM_AUTO, DECIM_SCAN, DECIM_WINDOW, DECIM_FULL = 0, 1, 2, 3
 # mavg_debug_force_cascade's paths (include/mavg_debug.h)
@@ -99,6 +104,8 @@ STAT_AUTO, STAT_TILE, STAT_STRIP = 0, 1, 2
 EXTREMA_AUTO, EXTREMA_TILE, EXTREMA_STRIP = 0, 1, 2
 # mavg_debug_force_ema's paths (include/mavg_debug.h)
 EMA_AUTO, EMA_TILE, EMA_CHAIN, EMA_STRIP = 0, 1, 2, 3
+# mavg_debug_force_biquad's paths (include/mavg_debug.h)
+BIQUAD_AUTO, BIQUAD_TILE, BIQUAD_CHAIN, BIQUAD_STRIP = 0, 1, 2, 3
 ABI_VERSION = 4
 DEBUG_LIB_PATH = os.path.join(_PKG, "lib", "libmavg_debug.so")
 # release flags + the test hooks (the forced-schedule parity tests time nothing, but they run the
@@ -199,6 +206,18 @@ def load(path: str = None) -> ctypes.CDLL:
     if hasattr(lib, "mavg_debug_force_ema"):  # debug and hooks builds only
         lib.mavg_debug_force_ema.argtypes = [i]
         lib.mavg_debug_force_ema.restype = i
+    coef5 = ctypes.POINTER(f64)  # five host doubles: b0 b1 b2 a1 a2
+    lib.mavg_biquad_run.argtypes = [vp, vp, sz, i, coef5, i, vp, vp, vp, sz, vp]
+    lib.mavg_biquad_run.restype = i
+    lib.mavg_biquad_workspace_bytes.argtypes = [sz, i, coef5, i, ctypes.POINTER(sz)]
+    lib.mavg_biquad_workspace_bytes.restype = i
+    lib.mavg_biquad_halo_frames.argtypes = [coef5, ctypes.POINTER(ctypes.c_longlong)]
+    lib.mavg_biquad_halo_frames.restype = i
+    lib.mavg_biquad_plan.argtypes = [sz, i, coef5, i, i, ctypes.c_char_p, sz]
+    lib.mavg_biquad_plan.restype = i
+    if hasattr(lib, "mavg_debug_force_biquad"):  # debug and hooks builds only
+        lib.mavg_debug_force_biquad.argtypes = [i]
+        lib.mavg_debug_force_biquad.restype = i
     lib.mavg_resolve_algo.argtypes = [sz, i, i, i, i]
     lib.mavg_resolve_algo.restype = i
     lib.mavg_plan.argtypes = [sz, i, i, i, i, i, ctypes.c_char_p, sz]

@@ -627,6 +627,66 @@ int ema_launch(int path, const EmaCall& a, Workspace ws, hipStream_t s) {
   return path == kEmaTile ? ema_tile_any(a.dtype, a.C, es, s) : ema_chain_any(a.dtype, a.C, es, ws, s);
 }
 
+// ---- biquad (mavg_biquad_run) -------------------------------------------------------------------
+// b0 b1 b2 a1 a2 finite, the poles strictly inside the unit circle (the stability triangle)
+int validate_biquad(size_t n, int C, const double* coef, int dtype) {
+  const int st = validate(n, C, 1, dtype, MAVG_ALGO_AUTO, 0);
+  if (st != MAVG_OK) return st;
+  if (coef == nullptr) return MAVG_ERR_INVALID_ARG;
+  for (int i = 0; i < 5; ++i)
+    if (!std::isfinite(coef[i])) return MAVG_ERR_INVALID_ARG;
+  const double a1 = coef[3], a2 = coef[4];
+  if (!(std::fabs(a2) < 1.0 && std::fabs(a1) < 1.0 + a2)) return MAVG_ERR_INVALID_ARG;
+  return MAVG_OK;
+}
+
+// The dispatch rule, in the order mavg.h gives; *path = kBiquadTile / kBiquadChain / kBiquadStrip.
+// The test hook's forced path replaces the rule: MAVG_ERR_UNSUPPORTED where the forced kernel cannot
+// take the shape (a tile past the stage limit, a tile or chain with three or more channels).
+int biquad_path(int C, long long halo, int dtype, int* path) {
+  const bool tile_ok = biquad_tile_fits(dtype, C, halo);
+  const bool chain_ok = C <= 2;
+  int forced = kBiquadAuto;
+#ifdef MAVG_TEST_HOOKS
+  forced = g_test_biquad_path.load(std::memory_order_relaxed);
+#endif
+  if ((forced == kBiquadTile && !tile_ok) || (forced == kBiquadChain && !chain_ok)) return MAVG_ERR_UNSUPPORTED;
+  *path = forced != kBiquadAuto ? forced : tile_ok ? kBiquadTile : chain_ok ? kBiquadChain : kBiquadStrip;
+  return MAVG_OK;
+}
+
+struct BiquadCall {
+  const void* in;
+  float* out;
+  const double* state_in;
+  double* state_out;
+  size_t n;
+  int C;
+  const double* coef;
+  long long halo;
+  int dtype;
+};
+
+// what mavg_biquad_workspace_bytes returns for a path
+int biquad_ws_bytes(int path, const BiquadCall& a, size_t* bytes) {
+  *bytes = 0;
+  if (path == kBiquadTile) return MAVG_OK;
+  const size_t nframes = a.n / (size_t)a.C;
+  return path == kBiquadChain ? biquad_chain_ws_bytes(nframes, a.C, bytes) : biquad_strip_ws_bytes(nframes, a.C, bytes);
+}
+
+// The launches of one path (plan mode when g_plan is set); views of any sample alignment: the
+// 16-B-unit form when d_in and d_out are 16-B aligned, else the frame-unit form over the whole
+// signal (no head is peeled).
+int biquad_launch(int path, const BiquadCall& a, Workspace ws, hipStream_t s) {
+  BiquadSig bs{a.in, a.out, a.state_in, a.state_out, a.n / (size_t)a.C,
+               {a.coef[0], a.coef[1], a.coef[2], a.coef[3], a.coef[4]}, a.halo};
+  if (path == kBiquadStrip) return biquad_strip_any(a.dtype, a.C, bs, ws, s);
+  bs.unit = aligned(a.in, 16) && aligned(a.out, 16);
+  bs.eio = !bs.unit && !aligned(a.in, elem_size(a.dtype) * (size_t)a.C) ? 1 : 0;
+  return path == kBiquadTile ? biquad_tile_any(a.dtype, a.C, bs, s) : biquad_chain_any(a.dtype, a.C, bs, ws, s);
+}
+
 // cascade_loop's workspace, in this order: the ping-pong buffer (the signal's bytes, 16-B padded);
 // with a history two block buffers of passes * (grade - 1) * C samples each (16-B padded); then
 // mavg_run's own workspace -- the signal's, and with a history at least the first block's.
@@ -1176,6 +1236,86 @@ int mavg_ema_run(const void* d_in, float* d_out, size_t n_samples, int channels,
   st = check_workspace(need, d_ws, ws_bytes);
   if (st != MAVG_OK) return st;
   return ema_launch(path, a, Workspace{d_ws, ws_bytes}, static_cast<hipStream_t>(stream));
+}
+
+int mavg_biquad_halo_frames(const double coef[5], long long* out_frames) {
+  if (out_frames == nullptr) return MAVG_ERR_INVALID_ARG;
+  const int st = validate_biquad(0, 1, coef, MAVG_F32);
+  if (st != MAVG_OK) return st;
+  *out_frames = biquad_halo_frames(coef);
+  return MAVG_OK;
+}
+
+int mavg_biquad_workspace_bytes(size_t n_samples, int channels, const double coef[5], int dtype, size_t* out_bytes) {
+  if (out_bytes == nullptr) return MAVG_ERR_INVALID_ARG;
+  int st = validate_biquad(n_samples, channels, coef, dtype);
+  if (st != MAVG_OK) return st;
+  *out_bytes = 0;
+  if (n_samples == 0) return MAVG_OK;
+  const long long halo = biquad_halo_frames(coef);
+  int path = kBiquadStrip;
+  st = biquad_path(channels, halo, dtype, &path);
+  if (st != MAVG_OK) return st;
+  const BiquadCall a{kPlanIn, static_cast<float*>(kPlanOut), nullptr, nullptr, n_samples, channels, coef, halo, dtype};
+  {
+    // the launches' own limit (grid_too_large) shows here as it does in mavg_biquad_run
+    PlanScope ps;
+    st = biquad_launch(path, a, Workspace{}, nullptr);
+    if (st != MAVG_OK) return st;
+  }
+  return biquad_ws_bytes(path, a, out_bytes);
+}
+
+int mavg_biquad_plan(size_t n_samples, int channels, const double coef[5], int dtype, int flags, char* buf,
+                     size_t buflen) {
+  if (buf == nullptr || buflen == 0) return MAVG_ERR_INVALID_ARG;
+  buf[0] = 0;
+  int st = validate_biquad(n_samples, channels, coef, dtype);
+  if (st != MAVG_OK) return st;
+  if (flags < 0 || flags > 7) return MAVG_ERR_INVALID_ARG;
+  if (n_samples == 0) return MAVG_ERR_INVALID_ARG;  // nothing to describe, as mavg_plan
+  const long long halo = biquad_halo_frames(coef);
+  int path = kBiquadStrip;
+  st = biquad_path(channels, halo, dtype, &path);
+  if (st != MAVG_OK) return st;
+  PlanScope ps;
+  // (flag 4: views off 16-B alignment -- an input one sample past a 16-B boundary)
+  const void* const in = (flags & 4) != 0 ? static_cast<const char*>(kPlanIn) + elem_size(dtype) : kPlanIn;
+  const double* const sin = (flags & 1) != 0 ? static_cast<const double*>(kPlanOff) : nullptr;
+  double* const sout = (flags & 2) != 0 ? static_cast<double*>(const_cast<void*>(kPlanOff)) + 64 : nullptr;
+  st = biquad_launch(path, BiquadCall{in, static_cast<float*>(kPlanOut), sin, sout, n_samples, channels, coef, halo, dtype},
+                     Workspace{}, nullptr);
+  if (st == MAVG_OK) snprintf(buf, buflen, "%s", ps.plan.text);
+  return st;
+}
+
+// One launch of the tile kernel where the rule (biquad_path) takes the coefficients' halo, else the
+// three launches of the chain or the strip form, all planned before the first is made.
+int mavg_biquad_run(const void* d_in, float* d_out, size_t n_samples, int channels, const double coef[5], int dtype,
+                    const double* d_state_in, double* d_state_out, void* d_ws, size_t ws_bytes, void* stream) {
+  int st = validate_biquad(n_samples, channels, coef, dtype);
+  if (st != MAVG_OK) return st;
+  if (d_state_in != nullptr && d_state_in == d_state_out) return MAVG_ERR_INVALID_ARG;
+  if (n_samples == 0) return MAVG_OK;
+  if (d_in == nullptr || d_out == nullptr) return MAVG_ERR_INVALID_ARG;
+  if (!aligned(d_in, elem_size(dtype)) || !aligned(d_out, 4) || !aligned(d_state_in, 8) || !aligned(d_state_out, 8))
+    return MAVG_ERR_MISALIGNED;
+  const long long halo = biquad_halo_frames(coef);
+  int path = kBiquadStrip;
+  st = biquad_path(channels, halo, dtype, &path);
+  if (st != MAVG_OK) return st;
+  const BiquadCall a{d_in, d_out, d_state_in, d_state_out, n_samples, channels, coef, halo, dtype};
+  {
+    PlanScope ps;  // every launch's limits, with nothing enqueued
+    st = biquad_launch(path, a, Workspace{}, nullptr);
+    if (st != MAVG_OK) return st;
+  }
+  size_t need = 0;
+  st = biquad_ws_bytes(path, a, &need);
+  if (st != MAVG_OK) return st;
+  st = check_workspace(need, d_ws, ws_bytes);
+  if (st != MAVG_OK) return st;
+  return biquad_launch(path, a, Workspace{d_ws, ws_bytes}, static_cast<hipStream_t>(stream));
 }
 
 int mavg_ragged_workspace_bytes(const int64_t* h_offsets, size_t rows, int channels, int grade, int dtype,

@@ -85,8 +85,9 @@ struct EmaLds {
 // tile (and halo) -> registers -> LDS, as stat_tile_kernel: thread tid takes units u * WG + tid;
 // a whole tile moves as 16-B units, non-temporal except the frames the next tile's halo re-reads;
 // a part tile and a halo that starts before frame 0 move as guarded elements (zeros outside).
-template <typename T, int C, int F, int U, int WG, int NT>
-__device__ __forceinline__ void ema_stage(const EmaParams& p, T* stage, long long t0, bool tile_full) {
+// P: EmaParams, or another family's parameters with in, nframes, halo_units and eio (mavg_biquad.hpp).
+template <typename T, int C, int F, int U, int WG, int NT, typename P>
+__device__ __forceinline__ void ema_stage(const P& p, T* stage, long long t0, bool tile_full) {
   constexpr int VE = F * C;
   constexpr int TF = WG * F * U;
   using IO = UnitIO<T, VE>;

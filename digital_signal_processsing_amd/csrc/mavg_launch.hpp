@@ -347,6 +347,48 @@ int ema_strip_any(int dtype, int C, const EmaSig& es, Workspace ws, hipStream_t 
 int ema_chain_ws_bytes(size_t nframes, int C, size_t* bytes);
 int ema_strip_ws_bytes(size_t nframes, int C, size_t* bytes);
 
+// The biquad (mavg_biquad.hpp, instantiated in mavg_biquad.hip): y[f] = b0 x[f] + b1 x[f-1] + b2
+// x[f-2] - a1 y[f-1] - a2 y[f-2], fp32 out; state_in / state_out: `C` x 2 doubles (the transposed
+// direct form II's s1, s2) in device memory or NULL.  coef: b0 b1 b2 a1 a2, validated (finite,
+// stable); halo: biquad_halo_frames(coef), formed once per call by the API.
+//   unit  the 16-B-unit form (in and out 16-B aligned); else the frame-unit (F = 1) form
+//   eio   frame-unit form on an input that is only element-aligned (UnitIO::gload)
+struct BiquadSig {
+  const void* in;
+  float* out;
+  const double* state_in;
+  double* state_out;
+  size_t nframes;
+  double coef[5];
+  long long halo;
+  bool unit = true;
+  int eio = 0;
+};
+// The test hook's forced path (mavg_debug_force_biquad, include/mavg_debug.h): 0 = the rule decides
+constexpr int kBiquadAuto = 0, kBiquadTile = 1, kBiquadChain = 2, kBiquadStrip = 3;
+#ifdef MAVG_TEST_HOOKS
+extern std::atomic<int> g_test_biquad_path;
+#endif
+// H: a frame count with sum_{n > H} |h[n]| <= 2^-30 sum_n |h[n]| for the impulse response h (mavg.h
+// says how it is formed); coef validated
+long long biquad_halo_frames(const double coef[5]);
+// Whether the one-launch tile kernel takes a halo of H frames (the dispatch rule, and what a forced
+// biquad_tile may run): channels 1 or 2, H * C * sample size of at most 16 KiB, and its LDS layout
+// (BiquadLds) inside lds_budget in both forms.
+bool biquad_tile_fits(int dtype, int C, long long H);
+// MAVG_ERR_UNSUPPORTED: the halo does not fit, or the launch would exceed grid_too_large
+int biquad_tile_any(int dtype, int C, const BiquadSig& bs, hipStream_t st);
+// The chain (channels 1 or 2, else MAVG_ERR_UNSUPPORTED) and the strip form (every channel count):
+// three launches through one record of two doubles per tile or strip and channel; every launch is
+// checked before the first is made.  MAVG_ERR_WORKSPACE / MAVG_ERR_MISALIGNED for the workspace.
+int biquad_chain_any(int dtype, int C, const BiquadSig& bs, Workspace ws, hipStream_t st);
+int biquad_strip_any(int dtype, int C, const BiquadSig& bs, Workspace ws, hipStream_t st);
+// What mavg_biquad_workspace_bytes returns for the two: the records of the smaller (frame-unit)
+// tile, so that a misaligned view fits, or of the strips, times C * 16 (a multiple of 16).
+// MAVG_ERR_UNSUPPORTED where the byte count leaves size_t.
+int biquad_chain_ws_bytes(size_t nframes, int C, size_t* bytes);
+int biquad_strip_ws_bytes(size_t nframes, int C, size_t* bytes);
+
 // ceil(k / F): the units a k-frame halo takes (TileParams / AheadParams halo_units)
 template <int F>
 constexpr size_t tile_halo_units(int k) { return (size_t)(((long long)k + F - 1) / F); }

@@ -699,6 +699,162 @@ int mavg_ema_halo_frames(double alpha, long long* out_frames);
 int mavg_ema_plan(size_t n_samples, int channels, double alpha, int dtype, int flags,
                   char* buf, size_t buflen);
 
+/* Biquad (second-order IIR section), per channel of an interleaved signal
+ * x[f*C + c]:
+ *
+ *   y[f] = b0 x[f] + b1 x[f-1] + b2 x[f-2] - a1 y[f-1] - a2 y[f-2]
+ *
+ * -- low-pass, high-pass, band-pass, peaking and shelving EQ, DC blockers,
+ * Butterworth sections, one section of lfilter / sosfilt.
+ *
+ * Layout and dtypes.  dtype is MAVG_F32 or MAVG_I16.  The output is ALWAYS fp32,
+ * for int16 input too (n_samples floats, in d_in's layout); it must not overlap
+ * d_in.  Everything is evaluated in fp64 and rounded once to fp32.
+ *
+ * Coefficients.  coef is five host doubles b0 b1 b2 a1 a2, normalised (a0 == 1).
+ * A non-finite value, or poles that are not strictly inside the unit circle --
+ * the accepted region is |a2| < 1 && |a1| < 1 + a2 -- is MAVG_ERR_INVALID_ARG.
+ * a1 = a2 = 0 is a 3-tap FIR; b = (1, 0, 0), a = (0, 0) is the converting copy.
+ *
+ * State.  Transposed direct form II, scipy.signal.lfilter's zi / zf for a
+ * normalised section:
+ *
+ *   y = b0 x + s1;   s1' = b1 x - a1 y + s2;   s2' = b2 x - a2 y
+ *
+ * d_state_in holds channels * 2 doubles, [c][0] = s1 and [c][1] = s2, in device
+ * memory, 8-B aligned; NULL means zeros (frames before the first read as zero).
+ * d_state_out (same shape, or NULL) receives the state after the last frame
+ * from the same call.  The two state pointers must not be equal
+ * (MAVG_ERR_INVALID_ARG: the tile kernel's first tiles read one while its last
+ * tile writes the other).  Passing chunk i's state_out as chunk i+1's state_in
+ * reproduces the one-shot output within the accuracy bar below -- NOT bitwise:
+ * the association of the fp64 sums depends on the tiling.
+ *
+ * Halo.  With h[n] the impulse response, G = sum |h[n]| and M the largest of
+ * |x| over the signal and |state_in|, H = mavg_biquad_halo_frames(coef) is a
+ * frame count for which the library bounds
+ *
+ *   sum_{n > H} |h[n]| <= 2^-30 G
+ *
+ * -- not necessarily the smallest.  The envelope's H is proved; the refined H
+ * below rests on an fp64 iteration whose rounding is ALLOWED 2^-32 G, an
+ * allowance that is not derived (the iteration's error grows like n eps max
+ * |u_n|) and is checked against the exact tail on a list of 80 filters and on
+ * real-pole cases (tests/test_biquad_abi.py).  How it is formed: G is bounded below by the
+ * largest of |b0|, |h[1]| and the gains at DC and at Nyquist.  With u_m =
+ * sum_j p1^j p2^(m-1-j) over the poles p1, p2 (|u_m| <= m rho^(m-1), rho the
+ * larger modulus) the response is h[n] = c1 u_n + c2 u_(n-1), c1 = b1 - a1 b0,
+ * c2 = b2 - a2 b0, which gives a pole envelope for every pole pair, |h[n]| <=
+ * |c1| n rho^(n-1) + |c2| (n-1) rho^(n-2), and for complex poles r e^(+-i theta)
+ * the tighter |h[n]| <= E r^n, E = (|c1| + |c2| / r) / |Im p|; the tail of the
+ * smaller one is summed in closed form.  Where that envelope reaches 2^-30 G
+ * within 16384 frames, it is taken on to 2^-32 G and the impulse response is
+ * iterated in fp64 up to there: H is then the first frame count whose iterated
+ * remainder is at most 2^-31 G (both: a pole envelope, and an iterated response
+ * with a bounded tail).  Otherwise H is the envelope's.  Poles within 2^-48 of
+ * the circle saturate H at 2^62.  The states satisfy s1 = y - b0 x and s2 = b2
+ * x - a2 y with |a2| < 1, so the dependence of a state the filter produced on
+ * frames more than H back is bounded by the same tail.  A d_state_in that no
+ * input produces decays with the poles alone: biquad_tile carries it for as
+ * many frames as the pole envelope needs to fall to 2^-30 G, in at most the
+ * first 16 tiles (see "Which states" below).
+ *
+ * Accuracy, every path, every output.  With y_ref the serial fp64 recurrence
+ * above,
+ *
+ *   |y - y_ref| <= 2^-23 |y_ref| + 2^-29 G M
+ *
+ * and d_state_out is within 2^-29 G M of the reference state of the same call
+ * (its own d_state_in), per component.
+ *
+ * Which states.  Both promises are made for a d_state_in the filter can reach:
+ * NULL (zeros), the d_state_out of an earlier call, or lfilter_zi scaled by the
+ * signal's level.  Any other d_state_in is accepted, but it excites the poles
+ * alone and answers up to 1 / theta above M: for it only the outputs' bar is
+ * promised (the 2^-23 |y_ref| term carries the larger response), and on
+ * biquad_tile only while that response falls to 2^-30 G M within the first 16
+ * tiles (tile_frames in the plan text; 16384 frames in the frame-unit form) --
+ * the state is not applied past them.  d_state_out is NOT promised for such a
+ * state: the serial fp64 reference itself is off by more than 2^-29 G M there
+ * (its rounding is amplified by about 1 / theta^2).  biquad_chain and
+ * biquad_strip apply every state without a horizon.
+ * Write D = min(1 + a1 + a2, 1 - a1 + a2): small when both poles sit near +1 or
+ * near -1, as for a Butterworth corner far below the sample rate.  The bar is
+ * promised for D >= 2^-22 (a corner of about 3.4 Hz at 44.1 kHz).  Below that the
+ * call still runs, but the cancellation of the fp64 scan grows as the poles
+ * approach +-1 (the entries of a power of the state matrix are 1 / theta larger
+ * than what they sum to) and nothing is promised.  The powers of the state
+ * matrix are formed on the host in long double and rounded once.  Nothing is
+ * promised for non-finite fp32 input.
+ *
+ * Ownership, stream and capture rules are mavg_ema_run's: no allocation, no
+ * synchronisation, every step planned before the first is launched, nothing
+ * enqueued unless MAVG_OK is returned (MAVG_ERR_HIP excepted).  The workspace
+ * needs no initialisation -- every record read is written earlier in the same
+ * call -- so a call may be captured into a graph with no memset node.
+ * n_samples == 0: MAVG_OK, nothing enqueued, d_state_out untouched.
+ *
+ * Status: MAVG_ERR_INVALID_ARG for a bad dtype, channels < 1, n_samples not a
+ * multiple of channels, a NULL coef, coefficients as above, equal state
+ * pointers, or a NULL view with work to do; MAVG_ERR_MISALIGNED for d_in off
+ * sample alignment, d_out off 4 B, a state pointer off 8 B or d_ws off 16 B;
+ * MAVG_ERR_WORKSPACE for ws_bytes too small; MAVG_ERR_UNSUPPORTED past the
+ * one-launch limit below.
+ *
+ * Dispatch, evaluated in this order (mavg_biquad_plan shows which).  With the
+ * state s = (s1, s2) the recurrence is s' = A s + B x, A = [[-a1, 1], [-a2, 0]];
+ * over m frames it composes to s_out = A^m s_in + b, so only the 2-vector b is
+ * scanned and every multiplier is a power of A.
+ *   biquad_tile   channels 1 or 2 and a halo H * channels * sample size of at
+ *                 most 16 KiB (the stage limit of every tile kernel here; measured
+ *                 1.09x (int16 mono at 16 KiB) to 2.14x faster than the forced
+ *                 chain at 256 B, 2, 8 and 16 KiB of halo, DESIGN.md "Biquad").
+ *                 One launch, no workspace.  A tile stages its H
+ *                 halo frames in front of its own and rebuilds its carry state
+ *                 from them.  The 16-B-unit form runs when d_in and d_out are
+ *                 16-B aligned; other views run the frame-unit form (F=1 in the
+ *                 plan text) over the whole signal.
+ *   biquad_chain  channels 1 or 2, any stable coefficients: three launches
+ *                 through one record of two doubles per tile and channel -- the
+ *                 tiles' aggregates, one workgroup that turns them in place
+ *                 into the tiles' carry states (and writes d_state_out), the
+ *                 tiles again from their carry states.  No truncation.
+ *   biquad_strip  three or more channels: the same three steps with one thread
+ *                 per strip of L frames and channel at both ends (L in the plan
+ *                 text) -- correct, not fast.
+ *
+ * Workspace (mavg_biquad_workspace_bytes): 0 for biquad_tile; for biquad_chain
+ * the record count of the smaller tile of the frame-unit form (1024 frames), so
+ * that a misaligned view fits, times channels * 16; for biquad_strip the strip
+ * count times channels * 16.  d_ws 16-B aligned.
+ *
+ * Supported maximum.  Each launch takes at most 2^32 - 1 work-items, as
+ * mavg_ema_run's; past it MAVG_ERR_UNSUPPORTED and nothing is enqueued.  Frame
+ * and sample indices are 64-bit wherever they are not tile-local; NOT tested
+ * past 2^31 samples.
+ */
+int mavg_biquad_run(const void* d_in, float* d_out, size_t n_samples, int channels,
+                    const double coef[5] /* host: b0 b1 b2 a1 a2, a0 == 1 */, int dtype,
+                    const double* d_state_in /* or NULL */, double* d_state_out /* or NULL */,
+                    void* d_ws, size_t ws_bytes, void* stream);
+
+/* Device workspace mavg_biquad_run needs for these arguments (see "Workspace"
+ * above); the argument checks and the one-launch limit are mavg_biquad_run's. */
+int mavg_biquad_workspace_bytes(size_t n_samples, int channels, const double coef[5], int dtype,
+                                size_t* out_bytes);
+
+/* H of "Halo" above: 0 for the copy, at most 2 for a1 = a2 = 0. */
+int mavg_biquad_halo_frames(const double coef[5], long long* out_frames);
+
+/* Describe, without launching anything, what mavg_biquad_run would do:
+ * "biquad_tile<dtype,C=..,F=..,U=..,nt=..> halo_frames=H state=0|1|2|3 ... tile_frames=N ...",
+ * "biquad_chain<...> halo_frames=H ... tile_frames=N records=R carry_chunk=K launches=3" or
+ * "biquad_strip dtype=.. C=.. L=.. strips=.. carry_chunk=K launches=3 ...".
+ * flags: 1 = a d_state_in, 2 = a d_state_out, 4 = views off 16-B alignment (the
+ * frame-unit form).  n_samples == 0 has no plan: MAVG_ERR_INVALID_ARG. */
+int mavg_biquad_plan(size_t n_samples, int channels, const double coef[5], int dtype, int flags,
+                     char* buf, size_t buflen);
+
 /* Describe, without launching anything, the kernel and launch geometry
  * mavg_run would use for these arguments on 16-B-aligned views
  * (e.g. "tile_scan<f32,...> grid=... block=256 ..."). */

@@ -80,6 +80,17 @@ int mavg_debug_force_extrema(int path);
  * (nothing changes). */
 int mavg_debug_force_ema(int path);
 
+/* TEST HOOK (parity tests and tools/bench_biquad.py): force mavg_biquad_run's
+ * path -- 0: the dispatch rule decides (the default), 1: biquad_tile,
+ * 2: biquad_chain, 3: biquad_strip -- with the semantics of
+ * mavg_debug_force_ema: a forced path that cannot take the shape (biquad_tile
+ * past its 16-KiB halo limit, biquad_tile or biquad_chain with three or more
+ * channels) makes mavg_biquad_run, mavg_biquad_plan and
+ * mavg_biquad_workspace_bytes return MAVG_ERR_UNSUPPORTED; the workspace query
+ * follows the forced path; the strip takes every shape.  Process-wide; returns
+ * MAVG_OK, or MAVG_ERR_INVALID_ARG for another value (nothing changes). */
+int mavg_debug_force_biquad(int path);
+
 #ifdef __cplusplus
 }
 #endif

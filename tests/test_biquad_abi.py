@@ -1,0 +1,400 @@
+"""The biquad's contract (mavg_biquad_run, mavg_biquad_workspace_bytes, mavg_biquad_halo_frames,
+mavg_biquad_plan in include/mavg.h; the hook mavg_debug_force_biquad in include/mavg_debug.h): the
+symbols, the status table with dummy pointers, the halo length against the impulse response, the
+dispatch rule as the plan text shows it -- each boundary on both sides -- the workspace formula, the
+forced paths, the kernels' resource report and the wrappers' argument checks.  No GPU.
+
+The rule that ships is the starting one: biquad_tile for one or two channels and a halo H * channels
+* sample size of at most 16 KiB (fp32 H <= 4096 / 2048, int16 H <= 8192 / 4096), biquad_chain for
+the other coefficients with one or two channels, biquad_strip for three or more channels."""
+import ctypes
+import os
+import re
+import subprocess
+import sys
+
+import pytest
+
+import digital_signal_processsing_amd as dsp
+from digital_signal_processsing_amd import _lib
+
+from biquad_ref import (COPY, FILTER_LIST, FIR3, REAL_POLE_CASES, biquad_gain, min_halo, rbj, tail_after)
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "digital_signal_processsing_amd", "csrc")
+SYMBOLS = ("mavg_biquad_run", "mavg_biquad_workspace_bytes", "mavg_biquad_halo_frames", "mavg_biquad_plan")
+HOOK = "mavg_debug_force_biquad"
+F32, I16 = _lib.F32, _lib.I16
+TILE, CHAIN, STRIP = "biquad_tile<", "biquad_chain<", "biquad_strip "
+CARRY_CHUNK = 2048
+STRIP_FRAMES = 64
+LP = rbj("LP", 0.05, 0.7071)          # a halo of about a hundred frames: the tile by every rule
+SLOW = rbj("HP", 1e-4, 0.7071)        # a halo of tens of thousands of frames: the chain
+
+
+def c5(coef):
+    return (ctypes.c_double * 5)(*coef)
+
+
+def test_symbols_are_exported_by_every_build_and_the_hook_only_by_debug_and_hooks():
+    for path in (_lib.LIB_PATH, _lib.DEBUG_LIB_PATH, _lib.HOOKS_LIB_PATH):
+        lib = _lib.load(path)
+        for name in SYMBOLS:
+            assert hasattr(lib, name), (path, name)
+        assert lib.mavg_abi_version() == _lib.ABI_VERSION == 4  # additive: the version stays
+    assert set(SYMBOLS) <= set(_lib.EXPORTED_SYMBOLS)
+    assert not hasattr(_lib.load(), HOOK)                       # the release build has no hook
+    assert hasattr(_lib.load(_lib.DEBUG_LIB_PATH), HOOK) and HOOK in _lib.DEBUG_SYMBOLS
+    assert hasattr(_lib.load(_lib.HOOKS_LIB_PATH), HOOK)
+    assert (_lib.BIQUAD_AUTO, _lib.BIQUAD_TILE, _lib.BIQUAD_CHAIN, _lib.BIQUAD_STRIP) == (0, 1, 2, 3)
+    lib = _lib.load()
+    assert len(lib.mavg_biquad_run.argtypes) == 11
+    assert len(lib.mavg_biquad_workspace_bytes.argtypes) == 5
+    assert len(lib.mavg_biquad_halo_frames.argtypes) == 2
+    assert len(lib.mavg_biquad_plan.argtypes) == 7
+
+
+def test_header_declarations_equal_the_exported_symbols():
+    with open(os.path.join(ROOT, "include", "mavg.h")) as f:
+        h = f.read()
+    code = re.sub(r"/\*.*?\*/", "", h, flags=re.S)
+    declared = re.findall(r"^(?:int|const char\*)\s+(mavg_\w+)\s*\(", code, flags=re.M)
+    assert sorted(declared) == sorted(_lib.EXPORTED_SYMBOLS)
+    assert re.search(r"#define MAVG_ABI_VERSION 4\b", h)
+    assert h.index("int mavg_ema_plan") < h.index("Biquad (second-order IIR section)")   # after the EMA block
+    block = h[h.index("Biquad (second-order IIR section)"):h.index("int mavg_biquad_run")]
+    block = re.sub(r"\s*\n \*\s*", " ", block)                    # the comment's line breaks
+    assert "NOT bitwise" in block and "NOT tested past 2^31 samples" in block
+    for word in ("2^-23", "2^-29 G M", "2^-30 G", "16 KiB", "no memset node", "must not be equal", "D >= 2^-22",
+                 "|a2| < 1 && |a1| < 1 + a2", "pole envelope", "iterated", "long double", "nothing is promised"):
+        assert word in block, word
+    with open(os.path.join(ROOT, "include", "mavg_debug.h")) as f:
+        assert re.search(r"^int mavg_debug_force_biquad\(int path\);", f.read(), flags=re.M)
+
+
+IN, OUT, SIN, SOUT, WS = 1 << 20, 1 << 30, 1 << 24, (1 << 24) + 64, 1 << 26
+NAN, INF = float("nan"), float("inf")
+
+
+def _run(n, C=1, coef=LP, dtype=F32, din=IN, dout=OUT, sin=None, sout=None, ws=None, wsb=0, path=None):
+    return _lib.load(path).mavg_biquad_run(din, dout, n, C, None if coef is None else c5(coef), dtype, sin, sout, ws, wsb,
+                                           None)
+
+
+def with_a(a1, a2):
+    return (1.0, 0.0, 0.0, a1, a2)
+
+
+@pytest.mark.parametrize("args,status", [
+    (dict(n=100, dtype=7), _lib.ERR_INVALID_ARG),                        # bad dtype
+    (dict(n=100, dtype=-1), _lib.ERR_INVALID_ARG),
+    (dict(n=100, C=0), _lib.ERR_INVALID_ARG),                            # channels < 1
+    (dict(n=9, C=2), _lib.ERR_INVALID_ARG),                              # a partial frame
+    (dict(n=100, coef=None), _lib.ERR_INVALID_ARG),                      # no coefficients
+    (dict(n=100, coef=(NAN, 0, 0, 0, 0)), _lib.ERR_INVALID_ARG),         # a non-finite coefficient, each place
+    (dict(n=100, coef=(1, INF, 0, 0, 0)), _lib.ERR_INVALID_ARG),
+    (dict(n=100, coef=(1, 0, -INF, 0, 0)), _lib.ERR_INVALID_ARG),
+    (dict(n=100, coef=(1, 0, 0, NAN, 0)), _lib.ERR_INVALID_ARG),
+    (dict(n=100, coef=(1, 0, 0, 0, NAN)), _lib.ERR_INVALID_ARG),
+    (dict(n=100, coef=with_a(0.0, 1.0)), _lib.ERR_INVALID_ARG),          # poles on the circle: a2 = 1
+    (dict(n=100, coef=with_a(0.0, -1.0)), _lib.ERR_INVALID_ARG),         # poles at +-1
+    (dict(n=100, coef=with_a(1.5, 0.5)), _lib.ERR_INVALID_ARG),          # a1 = 1 + a2: a pole at -1
+    (dict(n=100, coef=with_a(-1.5, 0.5)), _lib.ERR_INVALID_ARG),         # a pole at +1
+    (dict(n=100, coef=with_a(-2.0, 1.0)), _lib.ERR_INVALID_ARG),         # a double pole at +1
+    (dict(n=100, coef=with_a(0.0, 1.5)), _lib.ERR_INVALID_ARG),          # outside
+    (dict(n=100, coef=with_a(-2.5, 1.0)), _lib.ERR_INVALID_ARG),
+    (dict(n=100, coef=with_a(-1.5 + 2.0 ** -50, 0.5)), _lib.OK),         # just inside
+    (dict(n=100, coef=with_a(0.0, 1.0 - 2.0 ** -50), ws=WS, wsb=1 << 20), _lib.OK),
+    (dict(n=100, sin=SIN, sout=SIN), _lib.ERR_INVALID_ARG),              # equal state pointers
+    (dict(n=100, din=0), _lib.ERR_INVALID_ARG),                          # a NULL view with work to do
+    (dict(n=100, dout=0), _lib.ERR_INVALID_ARG),
+    (dict(n=100, din=IN + 2), _lib.ERR_MISALIGNED),                      # fp32 input off 4 B
+    (dict(n=100, dtype=I16, din=IN + 1), _lib.ERR_MISALIGNED),           # int16 input off 2 B
+    (dict(n=100, dout=OUT + 2), _lib.ERR_MISALIGNED),                    # the fp32 output off 4 B
+    (dict(n=100, dtype=I16, dout=OUT + 2), _lib.ERR_MISALIGNED),
+    (dict(n=100, sin=SIN + 4), _lib.ERR_MISALIGNED),                     # a state pointer off 8 B
+    (dict(n=100, sout=SOUT + 4), _lib.ERR_MISALIGNED),
+    (dict(n=100, coef=SLOW, ws=WS + 8, wsb=1 << 20), _lib.ERR_MISALIGNED),    # the chain's workspace off 16 B
+    (dict(n=100, coef=SLOW), _lib.ERR_WORKSPACE),                        # the chain without a workspace
+    (dict(n=5000, coef=SLOW, ws=WS, wsb=64), _lib.ERR_WORKSPACE),        # 5 records of 16 B: 80 bytes
+    (dict(n=300, C=3, ws=WS, wsb=95), _lib.ERR_WORKSPACE),               # the strip: 2 strips * 3 * 16 B: 96
+    (dict(n=0, din=0, dout=0), _lib.OK),                                 # nothing to do
+    (dict(n=0, dtype=9, din=0), _lib.ERR_INVALID_ARG),                   # validated before the no-op
+    (dict(n=0, coef=with_a(0.0, 2.0), din=0), _lib.ERR_INVALID_ARG),
+    (dict(n=0, sin=SIN, sout=SIN), _lib.ERR_INVALID_ARG),
+    # past the one-launch limit: 256 threads per 2048-frame tile from 2^35 frames; the frame-unit
+    # form (4 frames per thread) from 2^34; the strip (64 frames per thread and channel) from 2^38
+    (dict(n=1 << 35), _lib.ERR_UNSUPPORTED),
+    (dict(n=1 << 34, din=IN + 4), _lib.ERR_UNSUPPORTED),
+    (dict(n=1 << 34, dout=OUT + 4), _lib.ERR_UNSUPPORTED),
+    (dict(n=1 << 35, coef=SLOW), _lib.ERR_UNSUPPORTED),                  # the chain, before its workspace is looked at
+    (dict(n=3 << 38, C=3), _lib.ERR_UNSUPPORTED),
+])
+def test_biquad_run_validates_before_launch(args, status):
+    """Dummy pointers: every refusal comes before anything is enqueued.  (The two OK rows of the
+    coefficient checks would launch: they are asked of the plan instead.)"""
+    if status == _lib.OK and args.get("n"):
+        buf = ctypes.create_string_buffer(512)
+        assert _lib.load().mavg_biquad_plan(args["n"], 1, c5(args["coef"]), F32, 0, buf, len(buf)) == _lib.OK
+        return
+    assert _run(**args) == status
+
+
+def test_plan_and_workspace_query_validate():
+    lib = _lib.load()
+    buf = ctypes.create_string_buffer(512)
+    out = ctypes.c_size_t(7)
+    lp, bad = c5(LP), c5(with_a(0.0, 1.0))
+    assert lib.mavg_biquad_plan(100, 1, lp, F32, 0, None, 0) == _lib.ERR_INVALID_ARG
+    assert lib.mavg_biquad_plan(0, 1, lp, F32, 0, buf, len(buf)) == _lib.ERR_INVALID_ARG   # as mavg_plan
+    assert lib.mavg_biquad_plan(100, 1, lp, 5, 0, buf, len(buf)) == _lib.ERR_INVALID_ARG
+    assert lib.mavg_biquad_plan(100, 1, bad, F32, 0, buf, len(buf)) == _lib.ERR_INVALID_ARG
+    assert lib.mavg_biquad_plan(100, 1, None, F32, 0, buf, len(buf)) == _lib.ERR_INVALID_ARG
+    assert lib.mavg_biquad_plan(100, 0, lp, F32, 0, buf, len(buf)) == _lib.ERR_INVALID_ARG
+    assert lib.mavg_biquad_plan(101, 2, lp, F32, 0, buf, len(buf)) == _lib.ERR_INVALID_ARG
+    assert lib.mavg_biquad_plan(100, 1, lp, F32, 8, buf, len(buf)) == _lib.ERR_INVALID_ARG
+    assert lib.mavg_biquad_plan(1 << 35, 1, lp, F32, 0, buf, len(buf)) == _lib.ERR_UNSUPPORTED
+    assert lib.mavg_biquad_plan(1 << 34, 1, lp, F32, 4, buf, len(buf)) == _lib.ERR_UNSUPPORTED    # the frame-unit form
+    assert lib.mavg_biquad_plan(1 << 34, 1, lp, F32, 0, buf, len(buf)) == _lib.OK
+    assert buf.value.startswith(b"biquad_tile<f32,C=1,F=4,U=2,") and f" grid={(1 << 34) // 2048} ".encode() in buf.value
+    assert lib.mavg_biquad_workspace_bytes(100, 1, lp, F32, None) == _lib.ERR_INVALID_ARG
+    assert lib.mavg_biquad_workspace_bytes(100, 1, bad, F32, ctypes.byref(out)) == _lib.ERR_INVALID_ARG
+    assert lib.mavg_biquad_workspace_bytes(101, 2, lp, F32, ctypes.byref(out)) == _lib.ERR_INVALID_ARG
+    assert lib.mavg_biquad_workspace_bytes(1 << 35, 1, c5(SLOW), F32, ctypes.byref(out)) == _lib.ERR_UNSUPPORTED
+    assert lib.mavg_biquad_workspace_bytes(0, 1, c5(SLOW), F32, ctypes.byref(out)) == _lib.OK and out.value == 0
+    for s in (0, 1, 2, 3):
+        plan = dsp.biquad_plan(1 << 20, LP, state=bool(s & 1), return_state=bool(s & 2))
+        assert f" state={s} " in plan, plan
+
+
+def halo_holds(coef, H):
+    G = biquad_gain(coef)
+    return tail_after(coef, H) <= 2.0 ** -30 * G
+
+
+@pytest.mark.parametrize("kind", ["LP", "HP", "BP", "PK"])
+def test_halo_frames_on_the_filter_list(kind):
+    """sum_{n > H} |h[n]| <= 2^-30 G against the reference's impulse response, and the cap H <= 2
+    min_halo + 64, on the 80 RBJ filters (20 per kind)."""
+    worst = 0.0
+    for k, f, Q in FILTER_LIST:
+        if k != kind:
+            continue
+        coef = rbj(k, f, Q)
+        H, m = dsp.biquad_halo_frames(coef), min_halo(coef)
+        assert halo_holds(coef, H), (k, f, Q, H, m)
+        assert m <= H <= 2 * m + 64, (k, f, Q, H, m)
+        worst = max(worst, H / max(m, 1))
+    print(f"{kind}: the library's H is at most {worst:.3f} x the smallest")
+
+
+def test_halo_frames_real_poles_and_degenerate_cases():
+    lib = _lib.load()
+    out = ctypes.c_longlong(-1)
+    assert lib.mavg_biquad_halo_frames(c5(LP), None) == _lib.ERR_INVALID_ARG
+    assert lib.mavg_biquad_halo_frames(None, ctypes.byref(out)) == _lib.ERR_INVALID_ARG
+    for bad in (with_a(0.0, 1.0), with_a(2.0, 1.0), (NAN, 0, 0, 0, 0), with_a(-1.5, 0.5)):
+        assert lib.mavg_biquad_halo_frames(c5(bad), ctypes.byref(out)) == _lib.ERR_INVALID_ARG
+    for coef in REAL_POLE_CASES:                       # only the inequality
+        H = dsp.biquad_halo_frames(coef)
+        assert halo_holds(coef, H) and H >= min_halo(coef), (coef, H, min_halo(coef))
+    assert dsp.biquad_halo_frames(COPY) == 0
+    assert dsp.biquad_halo_frames((0.5, 0.0, 0.0, 0.0, 0.0)) == 0
+    assert dsp.biquad_halo_frames(FIR3) == 2 and dsp.biquad_halo_frames((1.0, 0.5, 0.0, 0.0, 0.0)) == 1
+    assert dsp.biquad_halo_frames((1.0, -1.8, 0.81, -1.8, 0.81)) == 0      # the zeros cancel the poles: h = delta
+    # a scipy-style row of six is divided by a0
+    assert dsp.biquad_halo_frames((2.0, 1.0, 0.5, 2.0, -1.8, 0.9)) == dsp.biquad_halo_frames((1.0, 0.5, 0.25, -0.9, 0.45))
+    # poles within the rounding of the circle: H saturates, the chain takes it
+    assert dsp.biquad_halo_frames(with_a(0.0, 1.0 - 2.0 ** -52)) == 1 << 62
+    assert dsp.biquad_plan(1 << 20, with_a(0.0, 1.0 - 2.0 ** -52)).startswith(CHAIN)
+
+
+N = 1 << 22  # frames below: n = N * C samples
+LIMIT = {(F32, 1): 4096, (F32, 2): 2048, (I16, 1): 8192, (I16, 2): 4096}   # halo frames in 16 KiB
+NAME = {F32: "f32", I16: "i16"}
+
+
+def lp_at_boundary(lim):
+    """(f_in, f_out): LP filters, Q 0.7071, adjacent in f, the first with the library's H <= lim and
+    the second with H > lim (H falls as f rises; the bisection keeps H(lo) > lim >= H(hi))."""
+    H = lambda f: dsp.biquad_halo_frames(rbj("LP", f, 0.7071))
+    lo, hi = 1e-5, 0.25
+    assert H(lo) > lim >= H(hi)
+    for _ in range(60):
+        mid = 0.5 * (lo + hi)
+        if H(mid) > lim:
+            lo = mid
+        else:
+            hi = mid
+    return hi, lo
+
+
+@pytest.mark.parametrize("dt,C", sorted(LIMIT))
+def test_the_tile_rule_on_both_sides_of_its_boundary(dt, C):
+    lim = LIMIT[(dt, C)]
+    F = 16 // (C * (4 if dt == F32 else 2))
+    U = 2 if dt == F32 else 4
+    f_in, f_out = lp_at_boundary(lim)
+    for f, inside in ((0.05, True), (2 * f_in, True), (f_in, True), (f_out, False), (f_out / 4, False)):
+        coef = rbj("LP", f, 0.7071)
+        H = dsp.biquad_halo_frames(coef)                          # the library's own H, not recomputed
+        assert (H <= lim) == inside, (f, H, lim)
+        plan = dsp.biquad_plan(N * C, coef, C, dt)
+        off = dsp.biquad_plan(N * C, coef, C, dt, aligned=False)
+        ws = dsp.biquad_workspace_bytes(N * C, coef, C, dt)
+        assert f" halo_frames={H} " in plan and f" halo_frames={H} " in off, plan
+        if inside:
+            assert plan.startswith(f"biquad_tile<{NAME[dt]},C={C},F={F},U={U},"), plan
+            assert f" tile_frames={256 * F * U} " in plan, plan
+            assert int(plan.split(" lds=")[1].split()[0]) <= 64 * 1024, plan
+            assert off.startswith(f"biquad_tile<{NAME[dt]},C={C},F=1,U=4,") and " tile_frames=1024 " in off, off
+            assert int(off.split(" lds=")[1].split()[0]) <= 64 * 1024, off
+            assert ws == 0
+        else:
+            assert plan.startswith(f"biquad_chain<{NAME[dt]},C={C},F={F},U={U},"), plan
+            tf = 256 * F * U
+            assert f" tile_frames={tf} records={N // tf} carry_chunk={CARRY_CHUNK} launches=3" in plan, plan
+            assert off.startswith(f"biquad_chain<{NAME[dt]},C={C},F=1,U=4,"), off
+            assert f" tile_frames=1024 records={N // 1024} carry_chunk={CARRY_CHUNK} launches=3" in off, off
+            assert ws == N // 1024 * C * 16                       # the smaller tile's records
+    Hin, Hout = dsp.biquad_halo_frames(rbj("LP", f_in, 0.7071)), dsp.biquad_halo_frames(rbj("LP", f_out, 0.7071))
+    assert Hin <= lim < Hout and Hout - Hin <= 8                  # the boundary itself, on both sides
+
+
+@pytest.mark.parametrize("dt", [F32, I16])
+def test_the_three_channel_classes_and_the_workspace_formula(dt):
+    for coef in (COPY, FIR3, LP, rbj("PK", 0.25, 30.0), REAL_POLE_CASES[1]):
+        for C in (1, 2):
+            assert dsp.biquad_plan(N * C, coef, C, dt).startswith(TILE)
+    assert " halo_frames=0 " in dsp.biquad_plan(N, COPY, 1, dt)
+    for coef in (rbj("LP", 5e-4, 0.7071), SLOW, rbj("HP", 7.8e-5, 0.5001)):
+        for C in (1, 2):
+            assert dsp.biquad_plan(N * C, coef, C, dt).startswith(CHAIN)
+    for C in (3, 5, 8, 11):
+        for coef in (COPY, LP, SLOW):
+            for frames in (1, 63, 64, 65, 1000003):
+                plan = dsp.biquad_plan(frames * C, coef, C, dt)
+                strips = -(-frames // STRIP_FRAMES)
+                assert plan.startswith(f"biquad_strip dtype={NAME[dt]} C={C} L={STRIP_FRAMES} strips={strips} "
+                                       f"carry_chunk={CARRY_CHUNK} launches=3"), plan
+                assert dsp.biquad_plan(frames * C, coef, C, dt, aligned=False) == plan
+                assert dsp.biquad_workspace_bytes(frames * C, coef, C, dt) == strips * C * 16
+    for frames in (1, 1023, 1024, 1025, 5000):                    # the chain: records of 1024-frame tiles
+        for C in (1, 2):
+            assert dsp.biquad_workspace_bytes(frames * C, SLOW, C, dt) == -(-frames // 1024) * C * 16
+
+
+FORCE_CHILD = r'''
+import sys
+sys.path.insert(0, "tests")
+import digital_signal_processsing_amd as dsp
+from digital_signal_processsing_amd import _lib
+from biquad_ref import rbj
+lib = _lib.load(_lib.DEBUG_LIB_PATH)
+D = _lib.DEBUG_LIB_PATH
+plan = lambda *a, **k: dsp.biquad_plan(*a, library=D, **k)
+ws = lambda *a, **k: dsp.biquad_workspace_bytes(*a, library=D, **k)
+LP, SLOW, COPY = rbj("LP", 0.05, 0.7071), rbj("HP", 1e-4, 0.7071), (1.0, 0.0, 0.0, 0.0, 0.0)
+def unsupported(fn, *a):
+    try:
+        fn(*a)
+        raise SystemExit(f"a forced path took a shape outside its range: {a}")
+    except dsp.MavgError as e:
+        assert e.status == _lib.ERR_UNSUPPORTED
+assert lib.mavg_debug_force_biquad(4) == _lib.ERR_INVALID_ARG and lib.mavg_debug_force_biquad(-1) == _lib.ERR_INVALID_ARG
+n = 1 << 20
+assert plan(n, LP).startswith("biquad_tile<") and plan(n, SLOW).startswith("biquad_chain<")     # the rule
+assert plan(3 * n, LP, 3).startswith("biquad_strip ")
+assert lib.mavg_debug_force_biquad(_lib.BIQUAD_STRIP) == _lib.OK
+for c, C, dt in ((LP, 1, _lib.F32), (SLOW, 2, _lib.I16), (COPY, 1, _lib.I16), (LP, 5, _lib.F32)):
+    assert plan(n * C, c, C, dt).startswith("biquad_strip ")
+    assert ws(n * C, c, C, dt) == n // 64 * C * 16
+assert lib.mavg_debug_force_biquad(_lib.BIQUAD_CHAIN) == _lib.OK
+for c, C, dt in ((LP, 1, _lib.F32), (SLOW, 2, _lib.I16), (COPY, 1, _lib.I16)):
+    assert plan(n * C, c, C, dt).startswith("biquad_chain<")
+    assert ws(n * C, c, C, dt) == n // 1024 * C * 16
+for fn in (plan, ws):
+    unsupported(fn, 3 * n, LP, 3)
+import ctypes
+c5 = lambda c: (ctypes.c_double * 5)(*c)
+assert lib.mavg_biquad_run(1 << 20, 1 << 30, 3 * n, 3, c5(LP), _lib.F32, None, None, 1 << 26, 1 << 30, None) == _lib.ERR_UNSUPPORTED
+assert lib.mavg_debug_force_biquad(_lib.BIQUAD_TILE) == _lib.OK
+assert plan(n, LP).startswith("biquad_tile<") and ws(n, LP) == 0
+for c, C, dt in ((LP, 3, _lib.F32), (SLOW, 1, _lib.F32), (rbj("LP", 5e-4, 0.7071), 1, _lib.I16), (SLOW, 2, _lib.I16)):
+    for fn in (plan, ws):
+        unsupported(fn, n * C, c, C, dt)
+    assert lib.mavg_biquad_run(1 << 20, 1 << 30, n * C, C, c5(c), dt, None, None, 1 << 26, 1 << 30, None) == _lib.ERR_UNSUPPORTED
+assert lib.mavg_debug_force_biquad(_lib.BIQUAD_AUTO) == _lib.OK
+assert plan(n, SLOW).startswith("biquad_chain<") and plan(n, LP).startswith("biquad_tile<")
+print("force hook ok")
+'''
+
+
+def test_force_hook_on_the_debug_build():
+    """The hook is process-wide state: exercised in a child process of its own."""
+    r = subprocess.run([sys.executable, "-c", FORCE_CHILD], cwd=ROOT, capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and "force hook ok" in r.stdout, (r.stdout[-2000:], r.stderr[-3000:])
+
+
+def test_every_instance_compiles_for_gfx950_without_scratch():
+    """The compiler's own resource report of csrc/mavg_biquad.hip: the tile kernel and the chain's two
+    ends in 8 instances each (two dtypes, one and two channels, two unit forms), the carry kernel
+    and four strip kernels, no scratch."""
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    if not os.path.exists(hipcc):
+        pytest.fail(f"{hipcc} not found: the resource report needs the compiler the library is built with")
+    r = subprocess.run([hipcc, "-O3", "-std=c++17", "--offload-arch=gfx950", "--cuda-device-only", "-c",
+                        "-Rpass-analysis=kernel-resource-usage", "-o", os.devnull, "mavg_biquad.hip"],
+                       cwd=CSRC, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    names = re.findall(r"Function Name: (\S+)", r.stderr)
+    scratch = [int(v) for v in re.findall(r"ScratchSize \[bytes/lane\]: (\d+)", r.stderr)]
+    assert len(names) == len(scratch) == 29, names
+    for kernel, count in (("biquad_tile_kernel", 8), ("biquad_agg_kernel", 8), ("biquad_apply_kernel", 8),
+                          ("biquad_carry_kernel", 1), ("biquad_strip_kernel", 4)):
+        assert sum(kernel in n for n in names) == count, (kernel, names)
+    assert all(s == 0 for s in scratch), list(zip(names, scratch))
+
+
+def test_wrappers_check_their_arguments():
+    import torch
+    x = torch.zeros(1000)
+    out = torch.zeros(1000)
+    assert dsp.biquad_coef((2.0, 1.0, 0.5, 2.0, -1.8, 0.9)) == (1.0, 0.5, 0.25, -0.9, 0.45)
+    assert dsp.biquad_coef([1, 0, 0, 0, 0]) == COPY
+    for bad in ((1, 0, 0, 0), (1, 0, 0, 0, 0, 0, 0), (1.0, 0.0, 0.0, 0.0, -1.8, 0.9), (1, 0, 0, NAN, 0),
+                (1, 0, 0, 0.0, 1.0), (1, 0, 0, -2.0, 1.0), (1, 0, 0, 1, 0.0, 1.0), 3.0):
+        with pytest.raises(ValueError):
+            dsp.biquad_coef(bad)
+        with pytest.raises(ValueError):
+            dsp.biquad_into(x, out, bad)
+    with pytest.raises(ValueError, match="a0 must be finite and non-zero"):
+        dsp.biquad(x, (1.0, 0.0, 0.0, 0.0, -1.8, 0.9))
+    with pytest.raises(ValueError, match="device tensor"):
+        dsp.biquad(x, LP)                                              # a host tensor
+    with pytest.raises(ValueError, match="device tensor"):
+        dsp.biquad_into(x, out, LP)
+    with pytest.raises(ValueError, match="out must be float32"):       # an int16 out
+        dsp.biquad_into(torch.zeros(1000, dtype=torch.int16), torch.zeros(1000, dtype=torch.int16), LP)
+    for m in (999, 1001, 0):
+        with pytest.raises(ValueError, match="out must hold"):
+            dsp.biquad_into(x, torch.zeros(m), LP)
+    with pytest.raises(ValueError, match="float64"):                   # a state of the wrong dtype
+        dsp.biquad_into(x, out, LP, state=torch.zeros(2))
+    with pytest.raises(ValueError, match="float64"):
+        dsp.biquad_into(x, out, LP, state_out=torch.zeros(2, dtype=torch.float32))
+    with pytest.raises(ValueError, match="channels x 2 = 4 values"):   # ... or size
+        dsp.biquad_into(x, out, LP, channels=2, state=torch.zeros(2, dtype=torch.float64))
+    with pytest.raises(ValueError, match="channels x 2 = 2 values"):
+        dsp.biquad_into(x, out, LP, state_out=torch.zeros(1, dtype=torch.float64))
+    with pytest.raises(ValueError, match="multiple of channels"):
+        dsp.biquad_into(torch.zeros(1001), torch.zeros(1001), LP, channels=2)
+    with pytest.raises(TypeError, match="float32 and int16"):
+        dsp.biquad_into(torch.zeros(1000, dtype=torch.float64), out, LP)
+    for bad in ([], [LP], [[1, 0, 0, 1, 0]], [(1.0, 0.0, 0.0, 0.0, -1.8, 0.9)]):
+        with pytest.raises(ValueError):
+            dsp.sos_filter(x, bad)
+    with pytest.raises(ValueError, match="device tensor"):
+        dsp.sos_filter(x, [(1.0, 0.0, 0.0, 1.0, -0.5, 0.1)])
+    for name in ("biquad", "biquad_into", "biquad_plan", "biquad_workspace_bytes", "biquad_halo_frames", "sos_filter"):
+        assert name in dsp.__all__ and callable(getattr(dsp, name))
