@@ -13,6 +13,7 @@ only for device memory and streams.
     y = moving_rms(x, grade=1024)                      # fp32 RMS / variance / std of the window, one launch
     lo, hi = moving_minmax(x, grade=1024)              # the window's minimum and maximum (peak envelope), one launch
     y = exponential_moving_average(x, alpha=0.05)      # y[f] = (1-a) y[f-1] + a x[f], fp32 (or span= / halflife= / tau=)
+    y = fir_filter(x, taps)                            # y[f] = sum_j taps[j] x[f-j], one fp64 fma chain per output, fp32
 
 Semantics: ``basics/profilable_moving_averager.cpp:14-37`` -- interleaved
 frames, window ``grade`` frames, zero history (or ``history``: the
@@ -24,8 +25,8 @@ from __future__ import annotations
 from typing import Optional
 
 from . import _lib
-from ._lib import (ALGOS, F32, I16, STATS, MavgError, MavgLibraryError, algo_name,  # noqa: F401
-                   strerror)
+from ._lib import (ALGOS, F32, FIR_AUTO, FIR_STRIP, FIR_TILE, I16, STATS, MavgError, MavgLibraryError,  # noqa: F401
+                   algo_name, strerror)
 
 __all__ = [
     "moving_average",
@@ -72,6 +73,10 @@ __all__ = [
     "biquad_workspace_bytes",
     "biquad_halo_frames",
     "sos_filter",
+    "fir_filter",
+    "fir_filter_into",
+    "fir_taps",
+    "fir_plan",
     "fill_synthetic",
     "workspace_bytes",
     "resolve_algo",
@@ -1154,6 +1159,86 @@ def sos_filter(x, sos, channels: int = 1, state=None, return_state: bool = False
     if return_state and x.numel() == 0 and state is not None:
         sout[0].copy_(state)
     return (out, sout[0]) if return_state else out
+
+
+def fir_taps(taps, device):
+    """The taps as mavg_fir_run reads them: a contiguous ``float64`` tensor on ``device``.  A list,
+    numpy array or host tensor is checked to be 1-D, non-empty and finite and copied there (any
+    dtype: the values are converted to fp64); a ``float64`` device tensor passes through unread --
+    the library never reads taps on the host, so non-finite device taps give non-finite outputs."""
+    torch = _torch()
+    if torch.is_tensor(taps) and taps.is_cuda:
+        if taps.dtype != torch.float64:
+            raise ValueError(f"device taps must be float64 (the kernels read fp64 taps), got {taps.dtype}")
+        if taps.dim() != 1 or taps.numel() < 1:
+            raise ValueError(f"taps must be 1-D and non-empty, got shape {tuple(taps.shape)}")
+        if taps.device != torch.device(device):
+            raise ValueError(f"taps are on {taps.device}, the signal on {torch.device(device)}")
+        return taps.contiguous()
+    if torch.is_tensor(taps):
+        t = taps.detach().to(torch.float64)
+    else:
+        import numpy as np
+        t = torch.from_numpy(np.array(taps, dtype=np.float64))     # a copy: the caller's array may be read-only
+    if t.dim() != 1 or t.numel() < 1:
+        raise ValueError(f"taps must be 1-D and non-empty, got shape {tuple(t.shape)}")
+    if not bool(torch.isfinite(t).all()):
+        raise ValueError("taps must be finite")
+    return t.contiguous().to(device)
+
+
+def fir_plan(n: int, ntaps: int, channels: int = 1, dtype: int = F32, history: bool = False, aligned: bool = True,
+             library: Optional[str] = None) -> str:
+    """What mavg_fir_run would do (nothing is launched): ``fir_tile<...> taps=T halo_frames=T-1 ...
+    tile_frames=N ...`` or ``fir_strip ... L=...``.  ``aligned=False``: for views off 16-B alignment
+    (``F=1``)."""
+    import ctypes
+    buf = ctypes.create_string_buffer(512)
+    flags = (1 if history else 0) | (0 if aligned else 4)
+    _lib.check(_lib.load(library).mavg_fir_plan(n, channels, ntaps, dtype, flags, buf, len(buf)), "mavg_fir_plan")
+    return buf.value.decode()
+
+
+def fir_filter_into(x, out, taps, channels: int = 1, history=None, stream=None, library: Optional[str] = None) -> None:
+    """Enqueue ``out = fir_filter(x)`` on ``stream`` (default: current), one launch, no workspace.
+
+    ``out``: a contiguous ``float32`` device tensor of ``x``'s size that does not overlap ``x``.
+    ``taps``: as ``fir_taps`` takes them (pass its result to keep host taps from being copied on
+    every call).  ``history``: the ``(ntaps-1) * channels`` samples in front of ``x``."""
+    torch = _torch()
+    frames, C = _decim_shape(x, channels)
+    dt = _dtype_code(x)
+    if out.dtype != torch.float32:
+        raise ValueError(f"out must be float32 (the filter is fp32 for every input dtype), got {out.dtype}")
+    if out.numel() != x.numel():
+        raise ValueError(f"out must hold x's {x.numel()} samples, got {out.numel()}")
+    _check_device_pair(x, out)
+    # (host taps are copied on the launch stream, which then owns their block)
+    h = _on_stream(stream, lambda: fir_taps(taps, x.device))
+    ntaps = h.numel()
+    hist_ptr = _history_ptr(history, x, (ntaps - 1) * C, "(ntaps-1)*channels")
+    st = _lib.load(library).mavg_fir_run(x.data_ptr(), out.data_ptr(), x.numel(), C, h.data_ptr(), ntaps, dt, hist_ptr,
+                                         _stream_handle(stream, x.device))
+    _lib.check(st, "mavg_fir_run")
+
+
+def fir_filter(x, taps, channels: int = 1, history=None, stream=None, library: Optional[str] = None):
+    """``y[f] = sum_j taps[j] x[f-j]`` per channel of ``x`` (fp32 or int16), as ``float32`` in
+    ``x``'s shape; ``taps[0]`` multiplies the newest frame.  Every output is the fp32 rounding of one
+    fp64 fma chain, oldest frame first, so every path, alignment and chunking with a ``history``
+    (the ``(ntaps-1) * channels`` samples in front of ``x``) gives the same bits."""
+    torch = _torch()
+    _check_device_x(x)
+    _decim_shape(x, channels)
+    _dtype_code(x)
+    C = channels if x.dim() == 1 else x.shape[1]
+    h = fir_taps(taps, x.device)
+    like = x.new_empty(0, dtype=torch.float32)  # _with_out's model: x's device, float32
+
+    def into(out):
+        fir_filter_into(x, out, h, channels=C, history=history, stream=stream, library=library)
+
+    return _with_out(like, stream, into, (x, history, h), tuple(x.shape))
 
 
 def fill_synthetic(n: int, dtype=None, seed: int = 0x5EED, offset: int = 0, dist: int = 0,

@@ -78,6 +78,8 @@ EXPORTED_SYMBOLS = (
     "mavg_biquad_workspace_bytes",
     "mavg_biquad_halo_frames",
     "mavg_biquad_plan",
+    "mavg_fir_run",
+    "mavg_fir_plan",
     "mavg_resolve_algo",
     "mavg_plan",
     "mavg_fill_synthetic",
@@ -90,7 +92,7 @@ EXPORTED_SYMBOLS = (
 # exported by the debug build only (include/mavg_debug.h)
 DEBUG_SYMBOLS = ("mavg_test_ahead_schedule", "mavg_debug_force_decim", "mavg_debug_force_cascade",
                  "mavg_debug_force_stat", "mavg_debug_force_extrema", "mavg_debug_force_ema",
-                 "mavg_debug_force_biquad")
+                 "mavg_debug_force_biquad", "mavg_debug_force_fir")
 # mavg_debug_force_decim's paths (include/mavg_debug.h)
 DECIM_AUTO, DECIM_SCAN, DECIM_WINDOW, DECIM_FULL = 0, 1, 2, 3
 # mavg_debug_force_cascade's paths (include/mavg_debug.h)
@@ -106,6 +108,8 @@ EXTREMA_AUTO, EXTREMA_TILE, EXTREMA_STRIP = 0, 1, 2
 EMA_AUTO, EMA_TILE, EMA_CHAIN, EMA_STRIP = 0, 1, 2, 3
 # mavg_debug_force_biquad's paths (include/mavg_debug.h)
 BIQUAD_AUTO, BIQUAD_TILE, BIQUAD_CHAIN, BIQUAD_STRIP = 0, 1, 2, 3
+# mavg_debug_force_fir's paths (include/mavg_debug.h)
+FIR_AUTO, FIR_TILE, FIR_STRIP = 0, 1, 2
 ABI_VERSION = 4
 DEBUG_LIB_PATH = os.path.join(_PKG, "lib", "libmavg_debug.so")
 # release flags + the test hooks (the forced-schedule parity tests time nothing, but they run the
@@ -218,6 +222,13 @@ def load(path: str = None) -> ctypes.CDLL:
     if hasattr(lib, "mavg_debug_force_biquad"):  # debug and hooks builds only
         lib.mavg_debug_force_biquad.argtypes = [i]
         lib.mavg_debug_force_biquad.restype = i
+    lib.mavg_fir_run.argtypes = [vp, vp, sz, i, vp, i, i, vp, vp]
+    lib.mavg_fir_run.restype = i
+    lib.mavg_fir_plan.argtypes = [sz, i, i, i, i, ctypes.c_char_p, sz]
+    lib.mavg_fir_plan.restype = i
+    if hasattr(lib, "mavg_debug_force_fir"):  # debug and hooks builds only
+        lib.mavg_debug_force_fir.argtypes = [i]
+        lib.mavg_debug_force_fir.restype = i
     lib.mavg_resolve_algo.argtypes = [sz, i, i, i, i]
     lib.mavg_resolve_algo.restype = i
     lib.mavg_plan.argtypes = [sz, i, i, i, i, i, ctypes.c_char_p, sz]

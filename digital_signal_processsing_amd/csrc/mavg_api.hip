@@ -573,6 +573,49 @@ int extrema_launch(int path, const ExtremaCall& a, hipStream_t s) {
   return extrema_tile_any(a.dtype, a.C, es, a.k, s);
 }
 
+// ---- FIR filter (mavg_fir_run) -----------------------------------------------------------------
+int validate_fir(size_t n, int C, int ntaps, int dtype) {
+  const int st = validate(n, C, 1, dtype, MAVG_ALGO_AUTO, 0);
+  if (st != MAVG_OK) return st;
+  if (ntaps < 1) return MAVG_ERR_INVALID_ARG;
+  if ((long long)(ntaps - 1) * (long long)C > 0x7fffffffLL) return MAVG_ERR_UNSUPPORTED;  // the history's samples
+  return MAVG_OK;
+}
+
+// The dispatch rule: *path = kFirTile wherever the tile kernel takes the taps (fir_tile_fits), else
+// kFirStrip.  The test hook's forced path replaces the rule: MAVG_ERR_UNSUPPORTED where the tile
+// kernel cannot take the shape.
+int fir_path(int C, int ntaps, int dtype, int* path) {
+  const bool tile_ok = fir_tile_fits(dtype, C, ntaps);
+  int forced = kFirAuto;
+#ifdef MAVG_TEST_HOOKS
+  forced = g_test_fir_path.load(std::memory_order_relaxed);
+#endif
+  if (forced == kFirTile && !tile_ok) return MAVG_ERR_UNSUPPORTED;
+  *path = forced != kFirAuto ? forced : tile_ok ? kFirTile : kFirStrip;
+  return MAVG_OK;
+}
+
+struct FirCall {
+  const void* in;
+  float* out;
+  const void* hist;
+  const double* taps;
+  size_t n;
+  int C, ntaps, dtype;
+};
+
+// The one launch of fir_tile / fir_strip (plan mode when g_plan is set); views of any sample
+// alignment: the 16-B-unit form when the input and the output are 16-B aligned, else the frame-unit
+// form over the whole signal (no head is peeled).
+int fir_launch(int path, const FirCall& a, hipStream_t s) {
+  FirSig fs{a.in, a.out, a.hist, a.taps, a.n / (size_t)a.C};
+  if (path == kFirStrip) return fir_strip_any(a.dtype, a.C, fs, a.ntaps, s);
+  fs.unit = aligned(a.in, 16) && aligned(a.out, 16);
+  fs.eio = !fs.unit && !aligned(a.in, elem_size(a.dtype) * (size_t)a.C) ? 1 : 0;
+  return fir_tile_any(a.dtype, a.C, fs, a.ntaps, s);
+}
+
 // ---- exponential moving average (mavg_ema_run) -----------------------------------------------
 int validate_ema(size_t n, int C, double alpha, int dtype) {
   const int st = validate(n, C, 1, dtype, MAVG_ALGO_AUTO, 0);
@@ -1316,6 +1359,44 @@ int mavg_biquad_run(const void* d_in, float* d_out, size_t n_samples, int channe
   st = check_workspace(need, d_ws, ws_bytes);
   if (st != MAVG_OK) return st;
   return biquad_launch(path, a, Workspace{d_ws, ws_bytes}, static_cast<hipStream_t>(stream));
+}
+
+int mavg_fir_plan(size_t n_samples, int channels, int ntaps, int dtype, int flags, char* buf, size_t buflen) {
+  if (buf == nullptr || buflen == 0) return MAVG_ERR_INVALID_ARG;
+  buf[0] = 0;
+  int st = validate_fir(n_samples, channels, ntaps, dtype);
+  if (st != MAVG_OK) return st;
+  if (flags < 0 || (flags & ~5) != 0) return MAVG_ERR_INVALID_ARG;
+  if (n_samples == 0) return MAVG_ERR_INVALID_ARG;  // nothing to describe, as mavg_plan
+  int path = kFirStrip;
+  st = fir_path(channels, ntaps, dtype, &path);
+  if (st != MAVG_OK) return st;
+  PlanScope ps;
+  // (flag 4: views off 16-B alignment -- an input one sample past a 16-B boundary)
+  const void* const in = (flags & 4) != 0 ? static_cast<const char*>(kPlanIn) + elem_size(dtype) : kPlanIn;
+  const void* const hist = (flags & 1) != 0 ? kPlanOff : nullptr;
+  st = fir_launch(path, FirCall{in, static_cast<float*>(kPlanOut), hist, static_cast<const double*>(kPlanOff), n_samples,
+                                channels, ntaps, dtype},
+                  nullptr);
+  if (st == MAVG_OK) snprintf(buf, buflen, "%s", ps.plan.text);
+  return st;
+}
+
+// One launch: the tile kernel where the rule (fir_path) takes the taps, else the strip kernel.
+int mavg_fir_run(const void* d_in, float* d_out, size_t n_samples, int channels, const double* d_taps, int ntaps,
+                 int dtype, const void* d_history, void* stream) {
+  int st = validate_fir(n_samples, channels, ntaps, dtype);
+  if (st != MAVG_OK) return st;
+  if (n_samples == 0) return MAVG_OK;
+  if (d_in == nullptr || d_out == nullptr || d_taps == nullptr) return MAVG_ERR_INVALID_ARG;
+  const size_t eb = elem_size(dtype);
+  if (!aligned(d_in, eb) || !aligned(d_out, 4) || !aligned(d_taps, 8) || (d_history != nullptr && !aligned(d_history, eb)))
+    return MAVG_ERR_MISALIGNED;
+  int path = kFirStrip;
+  st = fir_path(channels, ntaps, dtype, &path);
+  if (st != MAVG_OK) return st;
+  return fir_launch(path, FirCall{d_in, d_out, d_history, d_taps, n_samples, channels, ntaps, dtype},
+                    static_cast<hipStream_t>(stream));
 }
 
 int mavg_ragged_workspace_bytes(const int64_t* h_offsets, size_t rows, int channels, int grade, int dtype,

@@ -389,6 +389,35 @@ int biquad_strip_any(int dtype, int C, const BiquadSig& bs, Workspace ws, hipStr
 int biquad_chain_ws_bytes(size_t nframes, int C, size_t* bytes);
 int biquad_strip_ws_bytes(size_t nframes, int C, size_t* bytes);
 
+// The FIR filter (mavg_fir.hpp, instantiated in mavg_fir.hip): y[f] = sum_j taps[j] x[f-j], one
+// fp64 fma chain per output, fp32 out, one launch; taps: ntaps doubles in device memory; hist holds
+// ntaps - 1 frames or is NULL.
+//   unit  the 16-B-unit form (in and out 16-B aligned); else the frame-unit (F = 1) form
+//   eio   frame-unit form on an input that is only element-aligned (UnitIO::gload)
+struct FirSig {
+  const void* in;
+  float* out;
+  const void* hist;
+  const double* taps;
+  size_t nframes;
+  bool unit = true;
+  int eio = 0;
+};
+// The test hook's forced path (mavg_debug_force_fir, include/mavg_debug.h): 0 = the rule decides
+constexpr int kFirAuto = 0, kFirTile = 1, kFirStrip = 2;
+#ifdef MAVG_TEST_HOOKS
+extern std::atomic<int> g_test_fir_path;
+#endif
+// Whether the tile kernel takes this tap count (the dispatch rule, and what a forced fir_tile may
+// run): channels 1 or 2, a halo (ntaps - 1) * C * sample size of at most 16 KiB, and its LDS layout
+// (FirLds) inside lds_budget in both forms.
+bool fir_tile_fits(int dtype, int C, int ntaps);
+// MAVG_ERR_UNSUPPORTED: the taps do not fit, or the launch would exceed grid_too_large
+int fir_tile_any(int dtype, int C, const FirSig& fs, int ntaps, hipStream_t st);
+// The strip kernel: every channels, ntaps and sample-aligned view; kFirStripFrames frames per
+// thread.  MAVG_ERR_UNSUPPORTED: the launch would exceed grid_too_large.
+int fir_strip_any(int dtype, int C, const FirSig& fs, int ntaps, hipStream_t st);
+
 // ceil(k / F): the units a k-frame halo takes (TileParams / AheadParams halo_units)
 template <int F>
 constexpr size_t tile_halo_units(int k) { return (size_t)(((long long)k + F - 1) / F); }

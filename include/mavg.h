@@ -855,6 +855,80 @@ int mavg_biquad_halo_frames(const double coef[5], long long* out_frames);
 int mavg_biquad_plan(size_t n_samples, int channels, const double coef[5], int dtype, int flags,
                      char* buf, size_t buflen);
 
+/* FIR filter (finite impulse response), per channel of an interleaved signal
+ * x[f*channels + c] with the caller's taps h[0 .. ntaps-1]:
+ *
+ *     y[f] = sum_{j = 0 .. ntaps-1} h[j] * x[f-j]
+ *
+ * h[0] multiplies the newest frame.  dtype is MAVG_F32 or MAVG_I16; the output is
+ * always fp32, n_samples floats in d_in's layout, and must not overlap d_in.
+ *
+ * Taps.  d_taps holds ntaps doubles in DEVICE memory, 8-B aligned, caller-owned,
+ * read by the kernel on the stream.  The library never copies between host and
+ * device and never reads the taps on the host, so they are not validated: a
+ * non-finite tap gives non-finite outputs, not an error.  ntaps >= 1;
+ * (ntaps - 1) * channels must fit an int, else MAVG_ERR_UNSUPPORTED.
+ *
+ * History.  Frames before frame 0 read as zero; with d_history they read as the
+ * (ntaps - 1) * channels samples of dtype in front of d_in, oldest first -- the
+ * convention of mavg_run.  A signal cut into chunks, each passed the last
+ * ntaps - 1 frames before it, gives the one-shot outputs bit for bit.
+ *
+ * Arithmetic.  Each output is the fp32 rounding of ONE fp64 fma chain: the
+ * accumulator starts at +0.0, then acc = fma(h[j], (double)x[f-j], acc) for
+ * j = ntaps-1 down to 0 -- oldest frame first.  Zero-padded frames enter as
+ * fma(h[j], 0.0, acc) or are dropped, which gives the same bits.  No chain is
+ * split or reordered, so -- unlike the EMA and the biquad -- every path and form
+ * is bitwise equal: fir_tile, fir_strip, both unit forms, any tiling and any
+ * chunking with a history give the same bits for the same signal.
+ * The accuracy that follows: |y - y_ref| <= 2^-23 |y_ref| + 2^-36 G M with
+ * G = sum |h[j]|, M = max |x| over signal and history and y_ref the exact sum (a
+ * chain of T <= 8192 fmas errs by at most T 2^-53 G M <= 2^-40 G M; the bar
+ * leaves 16x for a reference's own rounding).  Longer tap sets scale the second
+ * term by ntaps / 8192.  Nothing is promised for non-finite input.
+ *
+ * Ownership, stream and capture rules are mavg_run's: no allocation, no
+ * synchronisation, no workspace, one launch; nothing is enqueued unless MAVG_OK
+ * is returned (MAVG_ERR_HIP excepted).  Arguments are validated first;
+ * n_samples == 0: MAVG_OK, nothing enqueued.
+ *
+ * Status: MAVG_ERR_INVALID_ARG for a bad dtype, channels < 1, ntaps < 1,
+ * n_samples not a multiple of channels, or a NULL d_in, d_out or d_taps with work
+ * to do; MAVG_ERR_MISALIGNED for d_in or d_history off sample alignment, d_out
+ * off 4 B or d_taps off 8 B; MAVG_ERR_UNSUPPORTED as above and past the
+ * one-launch limit below.
+ *
+ * Dispatch (mavg_fir_plan shows which):
+ *   fir_tile   channels 1 or 2 and a halo (ntaps - 1) * channels * sample size of
+ *              at most 16 KiB (the stage limit of every tile kernel here): fp32
+ *              up to 4097 taps mono and 2049 stereo, int16 up to 8193 and 4097.
+ *              A tile stages itself and its halo in LDS in the input's dtype; a
+ *              lane keeps the fp64 accumulators of R consecutive frames and feeds
+ *              every 16-B unit it reads from LDS to all of them; the taps arrive
+ *              as wave-uniform scalar loads.  The 16-B-unit form runs when d_in
+ *              and d_out are 16-B aligned; other views run the frame-unit form
+ *              (F=1 in the plan text) over the whole signal.
+ *   fir_strip  everything else -- three or more channels, longer tap sets: one
+ *              thread per channel of a strip of L frames (L in the plan text),
+ *              ntaps global reads per output -- correct, not fast.
+ *
+ * Supported maximum.  The launch takes at most 2^32 - 1 work-items, as
+ * mavg_run's; past it MAVG_ERR_UNSUPPORTED and nothing is enqueued.  Frame and
+ * sample indices are 64-bit wherever they are not tile-local;
+ * NOT tested past 2^31 samples.
+ */
+int mavg_fir_run(const void* d_in, float* d_out, size_t n_samples, int channels,
+                 const double* d_taps /* device: ntaps doubles */, int ntaps, int dtype,
+                 const void* d_history /* or NULL */, void* stream);
+
+/* Describe, without launching anything, what mavg_fir_run would do:
+ * "fir_tile<dtype,C=..,F=..,U=..,R=..> taps=T halo_frames=T-1 history=0|1 ... grid=.. block=.. lds=.. tile_frames=N ..."
+ * or "fir_strip dtype=.. C=.. taps=T L=.. strips=.. ...".
+ * flags: 1 = a d_history, 4 = views off 16-B alignment (the frame-unit form).
+ * n_samples == 0 has no plan: MAVG_ERR_INVALID_ARG. */
+int mavg_fir_plan(size_t n_samples, int channels, int ntaps, int dtype, int flags,
+                  char* buf, size_t buflen);
+
 /* Describe, without launching anything, the kernel and launch geometry
  * mavg_run would use for these arguments on 16-B-aligned views
  * (e.g. "tile_scan<f32,...> grid=... block=256 ..."). */

@@ -91,6 +91,15 @@ int mavg_debug_force_ema(int path);
  * MAVG_OK, or MAVG_ERR_INVALID_ARG for another value (nothing changes). */
 int mavg_debug_force_biquad(int path);
 
+/* TEST HOOK (parity tests and tools/bench_fir.py): force mavg_fir_run's path --
+ * 0: the dispatch rule decides (the default), 1: fir_tile, 2: fir_strip -- with
+ * the semantics of mavg_debug_force_extrema: a forced fir_tile that cannot take
+ * the shape (three or more channels, a halo past 16 KiB) makes mavg_fir_run and
+ * mavg_fir_plan return MAVG_ERR_UNSUPPORTED; the strip takes every shape.  Both
+ * paths give the same bits.  Process-wide; returns MAVG_OK, or
+ * MAVG_ERR_INVALID_ARG for another value (nothing changes). */
+int mavg_debug_force_fir(int path);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,282 @@
+"""The FIR filter's contract (mavg_fir_run, mavg_fir_plan in include/mavg.h; the hook
+mavg_debug_force_fir in include/mavg_debug.h): the symbols, the status table with dummy pointers,
+the dispatch rule as the plan text shows it -- each boundary on both sides -- the forced paths, the
+LDS layout at the boundary, the kernels' resource report and the wrappers' argument checks.  No GPU.
+
+The rule: fir_tile for one or two channels and a halo (ntaps - 1) * channels * sample size of at
+most 16 KiB (fp32 up to 4097 taps mono and 2049 stereo, int16 up to 8193 and 4097), fir_strip for
+everything else."""
+import ctypes
+import os
+import re
+import subprocess
+import sys
+
+import pytest
+
+import digital_signal_processsing_amd as dsp
+from digital_signal_processsing_amd import _lib
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "digital_signal_processsing_amd", "csrc")
+SYMBOLS = ("mavg_fir_run", "mavg_fir_plan")
+HOOK = "mavg_debug_force_fir"
+F32, I16 = _lib.F32, _lib.I16
+TILE, STRIP = "fir_tile<", "fir_strip "
+STRIP_FRAMES = 64
+NAME = {F32: "f32", I16: "i16"}
+LIMIT = {(F32, 1): 4097, (F32, 2): 2049, (I16, 1): 8193, (I16, 2): 4097}   # the last tap count of fir_tile
+
+
+def test_symbols_are_exported_by_every_build_and_the_hook_only_by_debug_and_hooks():
+    for path in (_lib.LIB_PATH, _lib.DEBUG_LIB_PATH, _lib.HOOKS_LIB_PATH):
+        lib = _lib.load(path)
+        for name in SYMBOLS:
+            assert hasattr(lib, name), (path, name)
+        assert lib.mavg_abi_version() == _lib.ABI_VERSION == 4  # additive: the version stays
+    assert set(SYMBOLS) <= set(_lib.EXPORTED_SYMBOLS)
+    assert not hasattr(_lib.load(), HOOK)                       # the release build has no hook
+    assert hasattr(_lib.load(_lib.DEBUG_LIB_PATH), HOOK) and HOOK in _lib.DEBUG_SYMBOLS
+    assert hasattr(_lib.load(_lib.HOOKS_LIB_PATH), HOOK)
+    assert (_lib.FIR_AUTO, _lib.FIR_TILE, _lib.FIR_STRIP) == (0, 1, 2)
+    assert (dsp.FIR_AUTO, dsp.FIR_TILE, dsp.FIR_STRIP) == (0, 1, 2)
+    lib = _lib.load()
+    assert len(lib.mavg_fir_run.argtypes) == 9
+    assert len(lib.mavg_fir_plan.argtypes) == 7
+
+
+def test_header_carries_the_contract():
+    with open(os.path.join(ROOT, "include", "mavg.h")) as f:
+        h = f.read()
+    code = re.sub(r"/\*.*?\*/", "", h, flags=re.S)
+    declared = re.findall(r"^(?:int|const char\*)\s+(mavg_\w+)\s*\(", code, flags=re.M)
+    assert sorted(declared) == sorted(_lib.EXPORTED_SYMBOLS)
+    assert re.search(r"#define MAVG_ABI_VERSION 4\b", h)
+    assert h.index("int mavg_biquad_plan") < h.index("FIR filter (finite impulse response)")   # after the biquad block
+    block = h[h.index("FIR filter (finite impulse response)"):h.index("int mavg_fir_run")]
+    for word in ("bitwise", "2^-23", "2^-36", "oldest frame first", "16 KiB", "NOT tested past 2^31 samples",
+                 "+0.0", "fma(h[j], (double)x[f-j], acc)", "never reads the taps on the host", "DEVICE memory"):
+        assert word in block, word
+    with open(os.path.join(ROOT, "include", "mavg_debug.h")) as f:
+        assert re.search(r"^int mavg_debug_force_fir\(int path\);", f.read(), flags=re.M)
+
+
+IN, OUT, TAPS, HIST = 1 << 20, 1 << 30, 1 << 24, 1 << 26
+
+
+def _run(n, C=1, ntaps=64, dtype=F32, din=IN, dout=OUT, taps=TAPS, hist=None, path=None):
+    return _lib.load(path).mavg_fir_run(din, dout, n, C, taps, ntaps, dtype, hist, None)
+
+
+@pytest.mark.parametrize("args,status", [
+    (dict(n=100, dtype=7), _lib.ERR_INVALID_ARG),                        # bad dtype
+    (dict(n=100, dtype=-1), _lib.ERR_INVALID_ARG),
+    (dict(n=100, C=0), _lib.ERR_INVALID_ARG),                            # channels < 1
+    (dict(n=100, C=-2), _lib.ERR_INVALID_ARG),
+    (dict(n=100, ntaps=0), _lib.ERR_INVALID_ARG),                        # ntaps < 1
+    (dict(n=100, ntaps=-5), _lib.ERR_INVALID_ARG),
+    (dict(n=9, C=2), _lib.ERR_INVALID_ARG),                              # a partial frame
+    (dict(n=100, din=0), _lib.ERR_INVALID_ARG),                          # a NULL view or NULL taps with work to do
+    (dict(n=100, dout=0), _lib.ERR_INVALID_ARG),
+    (dict(n=100, taps=0), _lib.ERR_INVALID_ARG),
+    (dict(n=100, din=IN + 2), _lib.ERR_MISALIGNED),                      # fp32 input off 4 B
+    (dict(n=100, dtype=I16, din=IN + 1), _lib.ERR_MISALIGNED),           # int16 input off 2 B
+    (dict(n=100, dout=OUT + 2), _lib.ERR_MISALIGNED),                    # the fp32 output off 4 B
+    (dict(n=100, dtype=I16, dout=OUT + 2), _lib.ERR_MISALIGNED),
+    (dict(n=100, taps=TAPS + 4), _lib.ERR_MISALIGNED),                   # the taps off 8 B
+    (dict(n=100, hist=HIST + 2), _lib.ERR_MISALIGNED),                   # the history off sample alignment
+    (dict(n=100, dtype=I16, hist=HIST + 1), _lib.ERR_MISALIGNED),
+    (dict(n=100, C=2, ntaps=(1 << 30) + 2), _lib.ERR_UNSUPPORTED),       # (ntaps - 1) * channels leaves int
+    (dict(n=99, C=3, ntaps=(1 << 31) - 1), _lib.ERR_UNSUPPORTED),
+    (dict(n=100, C=1, ntaps=(1 << 31) - 1, din=0), _lib.ERR_INVALID_ARG),   # ... which mono cannot: on to the NULL view
+    (dict(n=0, din=0, dout=0, taps=0), _lib.OK),                         # nothing to do
+    (dict(n=0, dtype=9, din=0), _lib.ERR_INVALID_ARG),                   # validated before the no-op
+    (dict(n=0, ntaps=0, din=0), _lib.ERR_INVALID_ARG),
+    (dict(n=0, C=0, din=0), _lib.ERR_INVALID_ARG),
+    # past the one-launch limit: 256 threads per 4096-frame tile reach 2^32 work-items at 2^36 frames;
+    # the frame-unit form (8 frames per thread) at 2^35; the strip (64 frames per thread and channel) at 2^38
+    (dict(n=1 << 36), _lib.ERR_UNSUPPORTED),
+    (dict(n=1 << 35, din=IN + 4), _lib.ERR_UNSUPPORTED),
+    (dict(n=1 << 35, dout=OUT + 4), _lib.ERR_UNSUPPORTED),
+    (dict(n=3 << 38, C=3), _lib.ERR_UNSUPPORTED),
+    (dict(n=1 << 38, ntaps=5000), _lib.ERR_UNSUPPORTED),
+])
+def test_fir_run_validates_before_launch(args, status):
+    assert _run(**args) == status
+
+
+def test_plan_validates_and_shows_the_limit():
+    lib = _lib.load()
+    buf = ctypes.create_string_buffer(512)
+    assert lib.mavg_fir_plan(100, 1, 64, F32, 0, None, 0) == _lib.ERR_INVALID_ARG
+    assert lib.mavg_fir_plan(0, 1, 64, F32, 0, buf, len(buf)) == _lib.ERR_INVALID_ARG      # as mavg_plan
+    assert lib.mavg_fir_plan(100, 1, 64, 5, 0, buf, len(buf)) == _lib.ERR_INVALID_ARG
+    assert lib.mavg_fir_plan(100, 1, 0, F32, 0, buf, len(buf)) == _lib.ERR_INVALID_ARG
+    assert lib.mavg_fir_plan(100, 0, 64, F32, 0, buf, len(buf)) == _lib.ERR_INVALID_ARG
+    assert lib.mavg_fir_plan(101, 2, 64, F32, 0, buf, len(buf)) == _lib.ERR_INVALID_ARG
+    for flags in (2, 3, 6, 8, -1):
+        assert lib.mavg_fir_plan(100, 1, 64, F32, flags, buf, len(buf)) == _lib.ERR_INVALID_ARG
+    assert lib.mavg_fir_plan(1 << 36, 1, 64, F32, 0, buf, len(buf)) == _lib.ERR_UNSUPPORTED
+    assert lib.mavg_fir_plan(1 << 35, 1, 64, F32, 4, buf, len(buf)) == _lib.ERR_UNSUPPORTED   # the frame-unit form
+    assert lib.mavg_fir_plan((1 << 36) - 4096, 1, 64, F32, 0, buf, len(buf)) == _lib.OK
+    assert buf.value.startswith(b"fir_tile<f32,C=1,F=4,U=4,R=16> taps=64 halo_frames=63 history=0 ")
+    assert f" grid={(1 << 24) - 1} ".encode() in buf.value
+    for hist in (False, True):
+        for C in (1, 3):
+            assert f" history={int(hist)} " in dsp.fir_plan(C << 20, 33, C, history=hist) + " "
+
+
+N = 1 << 22  # frames below: n = N * C samples
+
+
+@pytest.mark.parametrize("dt,C", sorted(LIMIT))
+def test_the_tile_rule_on_both_sides_of_its_boundary(dt, C):
+    lim = LIMIT[(dt, C)]
+    eb = 4 if dt == F32 else 2
+    assert (lim - 1) * C * eb == 16 * 1024
+    F = 16 // (C * eb)
+    U = 4 if dt == F32 else 2
+    R = U * F
+    for ntaps in (1, 2, F, F + 1, 64, lim // 2, lim - 1, lim):
+        plan = dsp.fir_plan(N * C, ntaps, C, dt)
+        off = dsp.fir_plan(N * C, ntaps, C, dt, aligned=False)
+        assert plan.startswith(f"fir_tile<{NAME[dt]},C={C},F={F},U={U},R={R}> taps={ntaps} halo_frames={ntaps - 1} history=0 "), plan
+        assert f" tile_frames={256 * R} " in plan and f" grid={N // (256 * R)} block=256 " in plan, plan
+        assert f" halo_units={-(-(ntaps - 1) // F)} " in plan, plan
+        assert int(plan.split(" lds=")[1].split()[0]) <= 64 * 1024, plan
+        assert off.startswith(f"fir_tile<{NAME[dt]},C={C},F=1,U=8,R=8> taps={ntaps} halo_frames={ntaps - 1} "), off
+        assert " tile_frames=2048 " in off and f" halo_units={ntaps - 1} " in off, off
+        assert int(off.split(" lds=")[1].split()[0]) <= 64 * 1024, off
+    for ntaps in (lim + 1, lim + 2, 4 * lim, 1 << 20):
+        plan = dsp.fir_plan(N * C, ntaps, C, dt)
+        assert plan.startswith(f"fir_strip dtype={NAME[dt]} C={C} taps={ntaps} L={STRIP_FRAMES} strips={N // STRIP_FRAMES} "), plan
+        assert dsp.fir_plan(N * C, ntaps, C, dt, aligned=False) == plan
+
+
+@pytest.mark.parametrize("dt", [F32, I16])
+def test_three_or_more_channels_take_the_strip(dt):
+    for C in (1, 2):
+        assert dsp.fir_plan(N * C, 100, C, dt).startswith(TILE)
+    for C in (3, 5, 8, 11):
+        for ntaps in (1, 2, 100, 5000):
+            for frames in (1, 63, 64, 65, 1000003):
+                plan = dsp.fir_plan(frames * C, ntaps, C, dt)
+                strips = -(-frames // STRIP_FRAMES)
+                assert plan.startswith(f"fir_strip dtype={NAME[dt]} C={C} taps={ntaps} L={STRIP_FRAMES} strips={strips} "), plan
+                assert dsp.fir_plan(frames * C, ntaps, C, dt, aligned=False) == plan
+
+
+def test_the_lds_layout_at_the_boundary_matches_the_model():
+    """FirLds as tests/test_fir_model.py restates it: the plan's lds at the boundary, both forms."""
+    for (dt, C), lim in LIMIT.items():
+        eb = 4 if dt == F32 else 2
+        for F, U in ((16 // (C * eb), 4 if dt == F32 else 2), (1, 8)):
+            for ntaps in (1, lim):
+                m = -(-(ntaps - 1) // F)
+                plane = (((m + U * 256 + U - 1) // U + 7) & ~7) + 8 // U
+                stage = (plane * U * F * C * eb + 15) & ~15
+                outs = (U * F * C // 4) * (256 + 4) * 16 if F > 1 else 0
+                plan = dsp.fir_plan(N * C, ntaps, C, dt, aligned=F > 1)
+                assert f",F={F},U={U}," in plan
+                lds = int(plan.split(" lds=")[1].split()[0])
+                assert lds == max(stage, outs) <= 64 * 1024, (plan, stage, outs)
+                assert (m + U * 256) * F * C * eb <= lds                 # the stage holds the halo and the tile
+
+
+FORCE_CHILD = r'''
+import digital_signal_processsing_amd as dsp
+from digital_signal_processsing_amd import _lib
+lib = _lib.load(_lib.DEBUG_LIB_PATH)
+D = _lib.DEBUG_LIB_PATH
+plan = lambda *a, **k: dsp.fir_plan(*a, library=D, **k)
+def unsupported(*a):
+    try:
+        plan(*a)
+        raise SystemExit(f"a forced tile took a shape outside its range: {a}")
+    except dsp.MavgError as e:
+        assert e.status == _lib.ERR_UNSUPPORTED
+assert lib.mavg_debug_force_fir(3) == _lib.ERR_INVALID_ARG and lib.mavg_debug_force_fir(-1) == _lib.ERR_INVALID_ARG
+n = 1 << 20
+assert plan(n, 64).startswith("fir_tile<") and plan(n, 5000).startswith("fir_strip ")     # the rule
+assert plan(3 * n, 64, 3).startswith("fir_strip ")
+assert lib.mavg_debug_force_fir(_lib.FIR_STRIP) == _lib.OK
+for nt, C, dt in ((1, 1, _lib.F32), (64, 1, _lib.F32), (4097, 2, _lib.I16), (9000, 1, _lib.I16), (3, 5, _lib.F32)):
+    assert plan(n * C, nt, C, dt).startswith("fir_strip "), (nt, C, dt)
+    assert plan(n * C, nt, C, dt, aligned=False).startswith("fir_strip ")
+assert lib.mavg_debug_force_fir(_lib.FIR_TILE) == _lib.OK
+for nt, C, dt in ((1, 1, _lib.F32), (64, 2, _lib.F32), (4097, 1, _lib.F32), (8193, 1, _lib.I16), (4097, 2, _lib.I16)):
+    assert plan(n * C, nt, C, dt).startswith("fir_tile<"), (nt, C, dt)
+for nt, C, dt in ((64, 3, _lib.F32), (4098, 1, _lib.F32), (2050, 2, _lib.F32), (8194, 1, _lib.I16), (4098, 2, _lib.I16),
+                  (1, 8, _lib.I16)):
+    unsupported(n * C, nt, C, dt)
+    assert lib.mavg_fir_run(1 << 20, 1 << 30, n * C, C, 1 << 24, nt, dt, None, None) == _lib.ERR_UNSUPPORTED
+assert lib.mavg_fir_run(0, 1 << 30, n, 1, 1 << 24, 64, _lib.F32, None, None) == _lib.ERR_INVALID_ARG   # validated first
+assert lib.mavg_debug_force_fir(_lib.FIR_AUTO) == _lib.OK
+assert plan(n, 5000).startswith("fir_strip ") and plan(n, 64).startswith("fir_tile<")
+print("force hook ok")
+'''
+
+
+def test_force_hook_on_the_debug_build():
+    """The hook is process-wide state: exercised in a child process of its own."""
+    r = subprocess.run([sys.executable, "-c", FORCE_CHILD], cwd=ROOT, capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and "force hook ok" in r.stdout, (r.stdout[-2000:], r.stderr[-3000:])
+
+
+def test_every_instance_compiles_for_gfx950_without_scratch():
+    """The compiler's own resource report of csrc/mavg_fir.hip: the tile kernel in 8 instances (two
+    dtypes, one and two channels, two unit forms) and two strip kernels; no scratch, and registers
+    that leave at least four waves per SIMD."""
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    if not os.path.exists(hipcc):
+        pytest.fail(f"{hipcc} not found: the resource report needs the compiler the library is built with")
+    r = subprocess.run([hipcc, "-O3", "-std=c++17", "--offload-arch=gfx950", "--cuda-device-only", "-c",
+                        "-Rpass-analysis=kernel-resource-usage", "-o", os.devnull, "mavg_fir.hip"],
+                       cwd=CSRC, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    names = re.findall(r"Function Name: (\S+)", r.stderr)
+    scratch = [int(v) for v in re.findall(r"ScratchSize \[bytes/lane\]: (\d+)", r.stderr)]
+    vgprs = [int(v) for v in re.findall(r" VGPRs: (\d+)", r.stderr)]
+    lds = [int(v) for v in re.findall(r"LDS Size \[bytes/block\]: (\d+)", r.stderr)]
+    assert len(names) == len(scratch) == len(vgprs) == len(lds) == 10, names
+    for kernel, count in (("fir_tile_kernel", 8), ("fir_strip_kernel", 2)):
+        assert sum(kernel in n for n in names) == count, (kernel, names)
+    assert all(s == 0 for s in scratch), list(zip(names, scratch))
+    assert all(v <= 128 for v in vgprs), list(zip(names, vgprs))         # 512 / 128: four waves per SIMD
+    assert all(b == 0 for b in lds), list(zip(names, lds))               # all LDS is dynamic (FirLds)
+
+
+def test_wrappers_check_their_arguments():
+    import numpy as np
+    import torch
+    x = torch.zeros(1000)
+    out = torch.zeros(1000)
+    taps = [0.5, 0.25, 0.25]
+    with pytest.raises(ValueError, match="device tensor"):
+        dsp.fir_filter(x, taps)                                        # a host tensor
+    with pytest.raises(ValueError, match="device tensor"):
+        dsp.fir_filter_into(x, out, taps)
+    with pytest.raises(ValueError, match="out must be float32"):       # an int16 out
+        dsp.fir_filter_into(torch.zeros(1000, dtype=torch.int16), torch.zeros(1000, dtype=torch.int16), taps)
+    for m in (999, 1001, 0):
+        with pytest.raises(ValueError, match="out must hold"):
+            dsp.fir_filter_into(x, torch.zeros(m), taps)
+    with pytest.raises(ValueError, match="multiple of channels"):
+        dsp.fir_filter_into(torch.zeros(1001), torch.zeros(1001), taps, channels=2)
+    with pytest.raises(ValueError, match="channels must be >= 1"):
+        dsp.fir_filter_into(x, out, taps, channels=0)
+    with pytest.raises(TypeError, match="float32 and int16"):
+        dsp.fir_filter_into(torch.zeros(1000, dtype=torch.float64), out, taps)
+    # host taps: 1-D, non-empty, finite; converted to contiguous fp64
+    for bad in ([], [[1.0, 2.0]], np.zeros((2, 2)), torch.zeros(0), 3.0):
+        with pytest.raises(ValueError, match="1-D and non-empty"):
+            dsp.fir_taps(bad, "cpu")
+    for bad in ([1.0, float("nan")], [float("inf")], np.array([1.0, -np.inf]), torch.tensor([float("nan")])):
+        with pytest.raises(ValueError, match="finite"):
+            dsp.fir_taps(bad, "cpu")
+    for good in ([1, 2, 3], np.arange(3, dtype=np.float32) + 1, torch.tensor([1.0, 2.0, 3.0])[::1], (1.0, 2.0, 3.0)):
+        t = dsp.fir_taps(good, "cpu")
+        assert t.dtype == torch.float64 and t.is_contiguous() and t.tolist() == [1.0, 2.0, 3.0]
+    assert dsp.fir_taps(torch.arange(6.0)[::2], "cpu").tolist() == [0.0, 2.0, 4.0]   # a strided view
+    for name in ("fir_filter", "fir_filter_into", "fir_taps", "fir_plan"):
+        assert name in dsp.__all__ and callable(getattr(dsp, name))
