@@ -576,7 +576,10 @@ int mavg_stat_plan(size_t n_samples, int channels, int grade, int stat, int dtyp
  * runs `block` threads per `tile_frames` frames (both in the plan text; the
  * frame-unit form, 4 frames per thread, refuses from 2^34 frames), extrema_strip
  * one thread per L frames and channel; past it MAVG_ERR_UNSUPPORTED and nothing
- * is enqueued.  Frame and sample indices are 64-bit; NOT tested past 2^31 samples.
+ * is enqueued.  Frame and sample indices are 64-bit.  extrema_tile (both unit
+ * forms, one output and both, the full 16-KiB halo, with and without a
+ * history) and extrema_strip are tested on 2^32 + 10^6-sample signals, every
+ * output (tests/test_gpu_bigsignal_filters.py).
  */
 int mavg_extrema_run(const void* d_in, void* d_max /* or NULL */, void* d_min /* or NULL */,
                      size_t n_samples, int channels, int grade, int dtype,
@@ -674,7 +677,10 @@ int mavg_extrema_plan(size_t n_samples, int channels, int grade, int dtype,
  * the frame-unit form, 4 frames per thread, refuses from 2^34 frames), the
  * strip kernels one thread per L frames and channel; past it
  * MAVG_ERR_UNSUPPORTED and nothing is enqueued.  Frame and sample indices are
- * 64-bit wherever they are not tile-local; NOT tested past 2^31 samples.
+ * 64-bit wherever they are not tile-local.  ema_tile (both unit forms, up to
+ * the 16-KiB halo, a state carried from an earlier chunk in and out), ema_chain
+ * (with a d_state_out) and ema_strip are tested on 2^32 + 10^6-sample signals,
+ * every output (tests/test_gpu_bigsignal_filters.py).
  */
 int mavg_ema_run(const void* d_in, float* d_out, size_t n_samples, int channels,
                  double alpha, int dtype,
@@ -830,8 +836,10 @@ int mavg_ema_plan(size_t n_samples, int channels, double alpha, int dtype, int f
  *
  * Supported maximum.  Each launch takes at most 2^32 - 1 work-items, as
  * mavg_ema_run's; past it MAVG_ERR_UNSUPPORTED and nothing is enqueued.  Frame
- * and sample indices are 64-bit wherever they are not tile-local; NOT tested
- * past 2^31 samples.
+ * and sample indices are 64-bit wherever they are not tile-local.  biquad_tile
+ * (both unit forms, a state carried from an earlier chunk in and out),
+ * biquad_chain (with a d_state_out) and biquad_strip are tested on 2^32 +
+ * 10^6-sample signals, every output (tests/test_gpu_bigsignal_filters.py).
  */
 int mavg_biquad_run(const void* d_in, float* d_out, size_t n_samples, int channels,
                     const double coef[5] /* host: b0 b1 b2 a1 a2, a0 == 1 */, int dtype,
@@ -914,8 +922,10 @@ int mavg_biquad_plan(size_t n_samples, int channels, const double coef[5], int d
  *
  * Supported maximum.  The launch takes at most 2^32 - 1 work-items, as
  * mavg_run's; past it MAVG_ERR_UNSUPPORTED and nothing is enqueued.  Frame and
- * sample indices are 64-bit wherever they are not tile-local;
- * NOT tested past 2^31 samples.
+ * sample indices are 64-bit wherever they are not tile-local.  fir_tile (both
+ * unit forms, 33 taps and the full 16-KiB halo, with and without a history) and
+ * fir_strip (three channels, 33 taps; not its long tap sets) are tested on 2^32 +
+ * 10^6-sample signals, every output (tests/test_gpu_bigsignal_filters.py).
  */
 int mavg_fir_run(const void* d_in, float* d_out, size_t n_samples, int channels,
                  const double* d_taps /* device: ntaps doubles */, int ntaps, int dtype,

@@ -18,7 +18,17 @@ not.  tests/test_bigsignal_ref.py pins this to the C oracle bit for bit.
 Siblings for the launchers built on the moving average, by the same walk:
   chunked_decim_mismatches    the kept frames phase + m * hop only, against the packed output
   chunked_cascade_mismatches  `passes` passes inside a chunk read with passes * (k-1) frames of lead
-  chunked_stat_mismatches     S1 and S2 of int16(-valued) input, the bars of tests/stat_ref.py"""
+  chunked_stat_mismatches     S1 and S2 of int16(-valued) input, the bars of tests/stat_ref.py
+
+And for the filters that are not built on it (second half of this file):
+  chunked_extrema_mismatches  the moving maximum and minimum by log-step doubling, bit patterns
+  chunked_fir_mismatches      exact fp64 sums of dyadic taps times int16-valued input, bit patterns
+  chunked_ema_mismatches      fp64 decayed doubling over a chunk read with W frames of lead, d^W <= 2^-60,
+  chunked_biquad_mismatches   the same on the state 2-vector, rho^W <= 2^-70; both against the bars
+                              of include/mavg.h, and both report the largest err / bar seen"""
+import math
+
+import numpy as np
 import torch
 
 
@@ -299,3 +309,252 @@ def chunked_stat_mismatches(x, y, mean, k, C, stat, chunk_frames, first_frame=0)
         del bad
         f0 = f1
     return count, first
+
+
+# ---- extrema, FIR, EMA, biquad: filters with kernels of their own ----
+def _chunks(F, W, chunk_frames, first_frame):
+    """(h0, f0, f1) of every chunk: frames [f0, f1) compared, read from frame h0 = max(0, f0 - W) on."""
+    f0 = first_frame
+    while f0 < F:
+        f1 = min(F, f0 + chunk_frames)
+        yield max(0, f0 - W), f0, f1
+        f0 = f1
+
+
+def _same_size(x, outs, dtype, what):
+    for t in outs:
+        if t is not None and (t.dtype != dtype or t.dim() != 1 or t.numel() != x.numel()):
+            raise ValueError(f"{what} must be 1-D {dtype} tensors of x's size")
+
+
+def _bits32(t):
+    return t.view(torch.int16 if t.element_size() == 2 else torch.int32)
+
+
+def chunked_extrema_mismatches(x, y_max, y_min, k, C, chunk_frames, first_frame=0):
+    """(count, first bad sample or None) of the moving maximum and / or minimum (either output may be
+    None, not both) of the causal k-frame window, truncated at frame 0 of ``x`` (frames before
+    first_frame are the history).  Exact: every output is one of the samples, bit patterns must be
+    equal; a sample counts once if either output is bad.  Per channel column, by log-step doubling:
+    r_1 = the column, r_2w[i] = op(r_w[i], r_w[i - w]) for i >= w (a frame closer than w to the
+    chunk's start already covers all of it), and a last step of k - w once 2 w > k."""
+    F = _check_signal(x, k, C, chunk_frames, first_frame)
+    if y_max is None and y_min is None:
+        raise ValueError("y_max and y_min must not both be None")
+    _same_size(x, (y_max, y_min), x.dtype, "y_max and y_min")
+    count, first = 0, None
+    for h0, f0, f1 in _chunks(F, k - 1, chunk_frames, first_frame):
+        nf, lead = f1 - f0, f0 - h0
+        xv = x[h0 * C:f1 * C].view(-1, C)
+        bad = torch.zeros((nf, C), dtype=torch.bool, device=x.device)
+        for y, op in ((y_max, torch.maximum), (y_min, torch.minimum)):
+            if y is None:
+                continue
+            yv = y[f0 * C:f1 * C].view(-1, C)
+            for c in range(C):
+                r, w = xv[:, c].clone(), 1
+                while 2 * w <= k:
+                    if w < r.numel():
+                        r[w:] = op(r[w:], r[:-w])     # (the right side is formed before it is stored)
+                    w *= 2
+                s = k - w
+                if 0 < s < r.numel():
+                    r[s:] = op(r[s:], r[:-s])
+                bad[:, c] |= _bits32(r[lead:]) != _bits32(yv[:, c].contiguous())
+                del r
+        count, first = _count(bad, f0 * C, count, first)
+        del bad
+    return count, first
+
+
+FIR_MAX_TAPS = 8193
+
+
+def dyadic_taps(ntaps, seed, sparse=False):
+    """ntaps host fp64 taps m / 1024, m a seeded integer in [-1024, 1024] that is never 0; with
+    ``sparse`` only taps 0, 1, ntaps-2, ntaps-1 and 12 seeded positions between are kept."""
+    rng = np.random.default_rng(seed)
+    m = rng.integers(1, 1025, ntaps) * rng.choice((-1, 1), ntaps)
+    if sparse:
+        keep = np.zeros(ntaps, dtype=bool)
+        keep[[0, 1, ntaps - 2, ntaps - 1]] = True
+        keep[rng.choice(np.arange(2, ntaps - 2), 12, replace=False)] = True
+        m = np.where(keep, m, 0)
+    return m.astype(np.float64) / 1024.0
+
+
+def chunked_fir_mismatches(x, y, taps, C, chunk_frames, first_frame=0):
+    """(count, first bad sample or None) of y[f] = sum_j taps[j] x[f-j] (fp32 ``y``, frames before
+    frame 0 of ``x`` read as zero, frames before first_frame are the history), bit for bit -- for
+    exact data only: ``x`` integer-valued with |x| <= 32768 and host fp64 taps m / 1024, |m| <= 1024
+    an integer, at most 8193 of them.  Every product and every partial sum is then a multiple of
+    2^-10 below 2^28 in magnitude: 38 bits, exact in fp64 in any order, with or without fma, so the
+    contract's chain is fl32(exact sum) and the reference adds h[j] * (the column shifted by j) in
+    fp64 over the NON-ZERO taps only."""
+    h = np.asarray(taps)
+    if h.dtype != np.float64 or h.ndim != 1 or not 1 <= h.size <= FIR_MAX_TAPS:
+        raise ValueError(f"taps: 1 to {FIR_MAX_TAPS} host float64 values")
+    m = h * 1024.0
+    if not (np.isfinite(m).all() and (m == np.rint(m)).all() and (np.abs(m) <= 1024).all()):
+        raise ValueError("taps must be m / 1024 with an integer |m| <= 1024: the fp64 sums would not be exact")
+    ntaps = h.size
+    F = _check_signal(x, ntaps, C, chunk_frames, first_frame)
+    _same_size(x, (y,), torch.float32, "y")
+    nz = [(j, float(h[j])) for j in range(ntaps) if h[j] != 0.0]
+    count, first = 0, None
+    for h0, f0, f1 in _chunks(F, ntaps - 1, chunk_frames, first_frame):
+        nf, lead = f1 - f0, f0 - h0
+        xv = x[h0 * C:f1 * C].view(-1, C)
+        yv = y[f0 * C:f1 * C].view(-1, C)
+        bad = torch.empty((nf, C), dtype=torch.bool, device=x.device)
+        for c in range(C):
+            col = xv[:, c].to(torch.float64)
+            if not bool(((col == col.round()) & (col.abs() <= 32768.0)).all()):
+                raise ValueError("FIR reference: inputs must be integer-valued with |x| <= 32768")
+            acc = torch.zeros(nf, dtype=torch.float64, device=x.device)
+            for j, hj in nz:
+                t0 = max(0, j - lead)            # frames of this chunk before it read x[f-j] = 0 (frame < 0)
+                if t0 < nf:
+                    acc[t0:].add_(col[lead + t0 - j:lead + nf - j], alpha=hj)
+            del col
+            bad[:, c] = acc.to(torch.float32).view(torch.int32) != yv[:, c].contiguous().view(torch.int32)
+            del acc
+        count, first = _count(bad, f0 * C, count, first)
+        del bad
+    return count, first
+
+
+def ema_lead(alpha):
+    """W: the smallest frame count with (1 - alpha)^W <= 2^-60."""
+    d = 1.0 - alpha
+    if d <= 0.0:
+        return 0
+    W = max(1, int(math.ceil(-60.0 * math.log(2.0) / math.log1p(-alpha))))
+    while d ** W > 2.0 ** -60:
+        W += 1
+    while W > 1 and d ** (W - 1) <= 2.0 ** -60:
+        W -= 1
+    return W
+
+
+def biquad_lead(coef):
+    """W: the smallest frame count with rho^W <= 2^-70, rho the larger pole modulus; at least 2."""
+    from biquad_ref import pole_radius
+    rho = pole_radius(coef)
+    if rho <= 0.0:
+        return 2
+    W = max(2, int(math.ceil(-70.0 * math.log(2.0) / math.log(rho))))
+    while rho ** W > 2.0 ** -70:
+        W += 1
+    while W > 2 and rho ** (W - 1) <= 2.0 ** -70:
+        W -= 1
+    return W
+
+
+def _ema_column(col, alpha, W):
+    """fp64 EMA of a chunk's column from a zero state in front of it, by decayed doubling:
+    e_0 = alpha x, e_(m+1)[f] = e_m[f] + d^(2^m) e_m[f - 2^m] until 2^m >= W."""
+    e = col.to(torch.float64).mul_(alpha)
+    d, s = np.longdouble(1.0) - np.longdouble(alpha), 1
+    while s < W:
+        if s < e.numel():
+            t = e[:-s] * float(d ** s)
+            e[s:] += t
+            del t
+        s *= 2
+    return e
+
+
+def _biquad_column(col, coef, W, nf):
+    """fp64 biquad outputs of the last nf frames of a chunk's column from a zero state in front of
+    it.  The state s = (s1, s2) after a frame obeys s' = A s + B x, A = [[-a1, 1], [-a2, 0]],
+    B = (b1 - a1 b0, b2 - a2 b0); S_0 = B x and S_(m+1)[f] = S_m[f] + A^(2^m) S_m[f - 2^m] until
+    2^m >= W, the matrices squared on the host in np.longdouble; then y[f] = b0 x[f] + s1[f-1]."""
+    b0, b1, b2, a1, a2 = (float(v) for v in coef)
+    x64 = col.to(torch.float64)
+    s1 = x64 * (b1 - a1 * b0)
+    s2 = x64 * (b2 - a2 * b0)
+    P = np.array([[-a1, 1.0], [-a2, 0.0]], dtype=np.longdouble)
+    s = 1
+    while s < W:
+        if s < x64.numel():
+            t1 = s1[:-s] * float(P[0, 0])
+            t1.add_(s2[:-s], alpha=float(P[0, 1]))
+            t2 = s1[:-s] * float(P[1, 0])
+            t2.add_(s2[:-s], alpha=float(P[1, 1]))
+            s1[s:] += t1
+            s2[s:] += t2
+            del t1, t2
+        P = P @ P
+        s *= 2
+    del s2
+    lead = x64.numel() - nf
+    ref = x64[lead:] * b0
+    if lead:
+        ref += s1[lead - 1:lead - 1 + nf]
+    else:
+        ref[1:] += s1[:nf - 1]
+    return ref
+
+
+def _chunked_recursive(x, y, C, M, chunk_frames, first_frame, W, column, abs_term, stats, keep):
+    F = _check_signal(x, 1, C, chunk_frames, first_frame)
+    if y is not None:
+        _same_size(x, (y,), torch.float32, "y")
+    if not (math.isfinite(M) and M >= 0.0):
+        raise ValueError("M must be finite and >= 0")
+    count, first, worst = 0, None, 0.0
+    for h0, f0, f1 in _chunks(F, W, chunk_frames, first_frame):
+        nf = f1 - f0
+        xv = x[h0 * C:f1 * C].view(-1, C)
+        bad = torch.empty((nf, C), dtype=torch.bool, device=x.device) if y is not None else None
+        for c in range(C):
+            ref = column(xv[:, c], nf)
+            if keep is not None:
+                keep[f0 * C + c:f1 * C:C] = ref.to(keep.device)
+            if y is not None:
+                err = (y[f0 * C:f1 * C].view(-1, C)[:, c].to(torch.float64) - ref).abs_()
+                bar = ref.abs_().mul_(2.0 ** -23).add_(abs_term)
+                bad[:, c] = ~(err <= bar)
+                if abs_term > 0.0:
+                    worst = max(worst, float(err.div_(bar).nan_to_num_(nan=math.inf).max()))
+                del err, bar
+            del ref
+        if y is not None:
+            count, first = _count(bad, f0 * C, count, first)
+            del bad
+    if stats is not None:
+        stats["worst"] = worst
+    return count, first
+
+
+def chunked_ema_mismatches(x, y, alpha, C, M, chunk_frames, first_frame=0, stats=None, keep=None):
+    """(count, first bad sample or None) of the outputs of frames >= first_frame outside the bar of
+    include/mavg.h, |y - ref| <= 2^-23 |ref| + 2^-29 M, with ref the fp64 EMA of the stream ``x``
+    from a zero state before its frame 0, formed per chunk by decayed doubling over ema_lead(alpha)
+    frames of lead (cut at frame 0, where the state is zero; past the lead a sample weighs at most
+    2^-60).  ``stats["worst"]`` receives the largest err / bar seen.  ``keep`` (a 1-D float64
+    tensor of x's size, for the tests of this reference itself) receives ref; ``y`` may then be None."""
+    if not 0.0 < alpha <= 1.0:
+        raise ValueError("alpha must lie in (0, 1]")
+    W = ema_lead(alpha)
+    return _chunked_recursive(x, y, C, M, chunk_frames, first_frame, W,
+                              lambda col, nf: _ema_column(col, alpha, W)[col.numel() - nf:],
+                              2.0 ** -29 * M, stats, keep)
+
+
+def chunked_biquad_mismatches(x, y, coef, C, G, M, chunk_frames, first_frame=0, stats=None, keep=None):
+    """chunked_ema_mismatches for the biquad ``coef`` = (b0, b1, b2, a1, a2): the bar is
+    |y - ref| <= 2^-23 |ref| + 2^-29 G M, the lead biquad_lead(coef) frames."""
+    if len(coef) != 5 or not (math.isfinite(G) and G >= 0.0):
+        raise ValueError("coef: five numbers; G finite and >= 0")
+    W = biquad_lead(coef)
+    return _chunked_recursive(x, y, C, M, chunk_frames, first_frame, W,
+                              lambda col, nf: _biquad_column(col, coef, W, nf),
+                              2.0 ** -29 * G * M, stats, keep)
+
+
+# The coefficients of the > 2^32-sample cases (tests/test_gpu_bigsignal_filters.py); the CPU tests of
+# this reference (tests/test_bigsignal_ref.py) measure it against the literal loops at the same ones.
+BIG_EMA_ALPHAS = (0.05, 0.01, 0.0051, 0.0026, 1e-4)
+BIG_BIQUADS = (("LP", 0.1, 0.707), ("LP", 0.002, 0.707), ("BP", 0.01, 4.0), ("HP", 0.0005, 0.7071))   # biquad_ref.rbj's kind, f, Q

@@ -332,3 +332,213 @@ def test_siblings_reject_what_they_cannot_check():
         chunked_stat_mismatches(xf + 0.5, xf, None, 2, 1, 0, 8)            # fp32: not integer-valued
     with pytest.raises(ValueError):
         chunked_stat_mismatches(xi, xf, None, 2, 5, 0, 8)                  # partial frame
+
+
+# ---- the filters with kernels of their own: extrema, FIR, EMA, biquad ----
+from bigsignal_ref import (BIG_BIQUADS, BIG_EMA_ALPHAS, biquad_lead, chunked_biquad_mismatches,  # noqa: E402
+                           chunked_ema_mismatches, chunked_extrema_mismatches, chunked_fir_mismatches, dyadic_taps,
+                           ema_lead)
+
+import biquad_ref  # noqa: E402
+import ema_ref  # noqa: E402
+import extrema_ref  # noqa: E402
+import fir_ref  # noqa: E402
+
+FR4 = 5 * 4096                # > 8193: the longest window and tap set leave their warm-up
+CH4 = (4096, 1009)            # divides FR4 / does not, and shorter than the leads of 4096 and 8192 frames
+FR5 = 10 * 4096               # EMA and biquad
+TAPS = {"dense33": dyadic_taps(33, 33), "sparse4097": dyadic_taps(4097, 4097, sparse=True)}
+
+
+@functools.lru_cache(maxsize=None)
+def _sig_dist(oracle_mod, C, dt, frames, dist):
+    n = frames * C
+    x = oracle_mod.synth_i16(n, seed=200 + C) if dt == "i16" else oracle_mod.synth_f32(n, seed=200 + C, dist=dist)
+    x.setflags(write=False)
+    return x
+
+
+@functools.lru_cache(maxsize=None)
+def _extrema_triple(oracle_mod, C, k, dt, ff):
+    """(x, max, min) of the whole stream; with ff = k - 1 its first frames are the history of the rest."""
+    x = _sig_dist(oracle_mod, C, dt, FR4, 2)
+    hist, sig = (x[:ff * C], x[ff * C:]) if ff else (None, x)
+    pad = np.full(ff * C, 21, x.dtype)
+    hi, lo = (np.concatenate([pad, a]) for a in extrema_ref.moving_extrema_ref(sig, k, C, hist))
+    return torch.from_numpy(x.copy()), torch.from_numpy(hi), torch.from_numpy(lo)
+
+
+@pytest.mark.parametrize("dt", ["i16", "f32"])
+@pytest.mark.parametrize("k", (1, 2, 64, 705, 8193))
+@pytest.mark.parametrize("C", (1, 2, 3))
+def test_extrema_reference_equals_extrema_ref(oracle_mod, C, k, dt):
+    for ff in sorted({0, k - 1}):
+        x, hi, lo = _extrema_triple(oracle_mod, C, k, dt, ff)
+        for chunk in CH4:
+            for a, b in ((hi, lo), (hi, None), (None, lo)):
+                assert chunked_extrema_mismatches(x, a, b, k, C, chunk, first_frame=ff) == (0, None), (ff, chunk)
+
+
+@pytest.mark.parametrize("dt", ["i16", "f32"])
+@pytest.mark.parametrize("C,k", [(1, 2), (2, 705), (3, 8193), (1, 64)])
+def test_extrema_single_flipped_bit_is_reported_at_its_index(oracle_mod, C, k, dt):
+    for ff in (0, k - 1):
+        x, hi, lo = _extrema_triple(oracle_mod, C, k, dt, ff)
+        n = x.numel()
+        for chunk in CH4:
+            mid = ff * C + ((FR4 - ff) // chunk // 2) * chunk * C
+            for i in (ff * C, mid - 1, mid, n - 1):
+                assert chunked_extrema_mismatches(x, _flip(hi, i), lo, k, C, chunk, first_frame=ff) == (1, i), (ff, chunk, i)
+                assert chunked_extrema_mismatches(x, hi, _flip(lo, i), k, C, chunk, first_frame=ff) == (1, i), (ff, chunk, i)
+                assert chunked_extrema_mismatches(x, None, _flip(lo, i), k, C, chunk, first_frame=ff) == (1, i)
+                assert chunked_extrema_mismatches(x, _flip(hi, i), None, k, C, chunk, first_frame=ff) == (1, i)
+                assert chunked_extrema_mismatches(x, hi, None, k, C, chunk, first_frame=ff) == (0, None)   # the flipped min not passed
+            if ff:
+                got = chunked_extrema_mismatches(x, _flip(hi, ff * C - 1), _flip(lo, ff * C - 1), k, C, chunk, first_frame=ff)
+                assert got == (0, None)
+        # a maximum and a minimum of one sample count once; the index is the lowest
+        got = chunked_extrema_mismatches(x, _flip(_flip(hi, n - 1), n // 2), _flip(lo, n // 2), k, C, CH4[1], first_frame=ff)
+        assert got == (2, n // 2)
+
+
+@functools.lru_cache(maxsize=None)
+def _fir_pair(oracle_mod, C, name, dt, with_history):
+    h = TAPS[name]
+    ff = h.size - 1 if with_history else 0
+    x = _sig_dist(oracle_mod, C, dt, FR4, 0)
+    hist, sig = (x[:ff * C], x[ff * C:]) if ff else (None, x)
+    y = np.concatenate([np.full(ff * C, 7.0, np.float32), fir_ref.fir_chain(sig, h, C, hist)])
+    return torch.from_numpy(x.copy()), torch.from_numpy(y), ff
+
+
+@pytest.mark.parametrize("dt", ["i16", "f32"])
+@pytest.mark.parametrize("C,name", [(1, "dense33"), (2, "dense33"), (3, "dense33"), (1, "sparse4097"), (2, "sparse4097")])
+def test_fir_reference_equals_the_contracts_chain(oracle_mod, C, name, dt):
+    """Bit-equal to fir_ref.fir_chain (fp64, oldest frame first, every tap) while it adds the
+    non-zero taps only, in another order; a flipped bit is found at exactly its index."""
+    h = TAPS[name]
+    assert h[0] != 0 and h[1] != 0 and h[-2] != 0 and h[-1] != 0
+    assert np.count_nonzero(h) == (33 if name == "dense33" else 16)
+    for with_history in (False, True):
+        x, y, ff = _fir_pair(oracle_mod, C, name, dt, with_history)
+        n = x.numel()
+        for chunk in CH4:
+            assert chunked_fir_mismatches(x, y, h, C, chunk, first_frame=ff) == (0, None), (with_history, chunk)
+            mid = ff * C + ((FR4 - ff) // chunk // 2) * chunk * C
+            for i in (ff * C, mid - 1, mid, n - 1):
+                assert chunked_fir_mismatches(x, _flip(y, i), h, C, chunk, first_frame=ff) == (1, i), (with_history, chunk, i)
+            if ff:
+                assert chunked_fir_mismatches(x, _flip(y, ff * C - 1), h, C, chunk, first_frame=ff) == (0, None)
+        y3 = _flip(_flip(_flip(y, n - 1), n // 2), ff * C + 5 * C)
+        assert chunked_fir_mismatches(x, y3, h, C, CH4[1], first_frame=ff) == (3, ff * C + 5 * C)
+
+
+def test_fir_reference_refuses_inexact_data():
+    xi = torch.zeros(64, dtype=torch.int16)
+    xf = torch.zeros(64, dtype=torch.float32)
+    ok = np.array([0.5, -1.0, 3.0 / 1024.0])
+    assert chunked_fir_mismatches(xi, xf, ok, 1, 16) == (0, None)
+    assert chunked_fir_mismatches(xf + 32768.0, xf, np.array([0.0]), 1, 16) == (0, None)
+    for bad in (np.array([0.1]), np.array([1.0 / 2048.0]), np.array([1025.0 / 1024.0]), np.array([np.nan]),
+                np.zeros(8194), np.zeros(0), np.array([0.5], dtype=np.float32)):
+        with pytest.raises(ValueError):
+            chunked_fir_mismatches(xi, xf, bad, 1, 16)
+    with pytest.raises(ValueError):
+        chunked_fir_mismatches(xf + 0.5, xf, ok, 1, 16)                    # not integer-valued
+    with pytest.raises(ValueError):
+        chunked_fir_mismatches(xf + 32769.0, xf, ok, 1, 16)                # past the 38-bit argument
+    with pytest.raises(ValueError):
+        chunked_fir_mismatches(xi, xi, ok, 1, 16)                          # the output is fp32
+    with pytest.raises(ValueError):
+        chunked_fir_mismatches(xi, xf, ok, 5, 16)                          # partial frame
+    with pytest.raises(ValueError):
+        chunked_extrema_mismatches(xi, None, None, 3, 1, 16)
+    with pytest.raises(ValueError):
+        chunked_extrema_mismatches(xi, xf, None, 3, 1, 16)                 # an extremum has x's dtype
+    with pytest.raises(ValueError):
+        chunked_ema_mismatches(xi, xf, 0.0, 1, 1.0, 16)
+    with pytest.raises(ValueError):
+        chunked_ema_mismatches(xi, xi, 0.5, 1, 1.0, 16)                    # the output is fp32
+
+
+def _chunks_for(W):
+    """Chunk sizes that divide FR5 and that do not, one of them shorter than the lead W."""
+    return (8192, 3001) + ((333,) if W <= 3001 else ())
+
+
+def _tamper_recursive(check, y):
+    """Bit 20 of an fp32 pattern is found at its index; one ulp (bit 0) is not.  One ulp is at most
+    2^-23 |v| / m for a mantissa m in [1, 2); with the output's own half ulp, bit 0 stays inside the
+    bar's 2^-23 |ref| wherever m >= 1.5, so those are the samples flipped."""
+    n = y.numel()
+    m, _ = np.frexp(np.abs(y.numpy()))
+    cand = np.nonzero(m >= 0.75)[0]
+    picks = [int(cand[0]), int(cand[cand.size // 2]), int(cand[-1])]
+    assert picks[0] < n // 100 and picks[-1] > n - n // 100
+    for i in picks:
+        assert check(_flip(y, i, 0)) == (0, None), i
+        assert check(_flip(y, i, 20)) == (1, i), i
+    assert check(_flip(_flip(y, picks[2], 20), picks[1], 20)) == (2, picks[1])
+
+
+@pytest.mark.parametrize("dt", ["i16", "f32"])
+@pytest.mark.parametrize("alpha", BIG_EMA_ALPHAS)
+@pytest.mark.parametrize("C", (1, 2))
+def test_ema_reference_against_the_literal_loop(oracle_mod, C, alpha, dt):
+    """The doubling reference's own output against ema_ref.ema_loop: the condition is 2^-35 M
+    (2.9e-11 M, 1/64 of the bar's absolute term).  Measured over these cases (40 960 frames, every chunking): at most 1.0e-15 M (int16 stereo, alpha = 1e-4)."""
+    x = _sig_dist(oracle_mod, C, dt, FR5, 2)
+    M = ema_ref.ema_scale(x)
+    loop = ema_ref.ema_loop(x, alpha, C)
+    xt = torch.from_numpy(x.copy())
+    y = torch.from_numpy(loop.astype(np.float32))
+    W = ema_lead(alpha)
+    assert (1.0 - alpha) ** W <= 2.0 ** -60 < (1.0 - alpha) ** (W - 1)
+    for chunk in _chunks_for(W):
+        keep = torch.full((x.size,), float("nan"), dtype=torch.float64)
+        stats = {}
+        assert chunked_ema_mismatches(xt, y, alpha, C, M, chunk, stats=stats, keep=keep) == (0, None), chunk
+        dev = float(np.abs(keep.numpy() - loop).max()) / M
+        print(f"ema {dt} C={C} alpha={alpha} chunk={chunk}: |ref - loop| <= {dev:.2e} M, worst err / bar {stats['worst']:.3f}")
+        assert dev <= 2.0 ** -35, (chunk, dev)
+        assert 0.0 < stats["worst"] <= 1.0
+    # from a given frame on: what precedes it is not looked at, the frame itself is
+    ff = 12345
+    junk = y.clone()
+    junk[:ff * C] = 7.0
+    assert chunked_ema_mismatches(xt, junk, alpha, C, M, 3001, first_frame=ff) == (0, None)
+    assert chunked_ema_mismatches(xt, _flip(junk, ff * C, 20), alpha, C, M, 3001, first_frame=ff) == (1, ff * C)
+    _tamper_recursive(lambda t: chunked_ema_mismatches(xt, t, alpha, C, M, 3001), y)
+
+
+@pytest.mark.parametrize("dt", ["i16", "f32"])
+@pytest.mark.parametrize("kind,f,Q", BIG_BIQUADS)
+@pytest.mark.parametrize("C", (1, 2))
+def test_biquad_reference_against_the_literal_loop(oracle_mod, C, kind, f, Q, dt):
+    """The doubling reference's own output against biquad_ref.biquad_loop: the condition is
+    2^-35 G M (2.9e-11 G M).  Measured over these cases (40 960 frames, every
+    chunking): at most 3.5e-13 G M (int16, RBJ HP f = 0.0005 Q = 0.7071); 2.2e-14 G M for the next worst (LP f = 0.002)."""
+    coef = biquad_ref.rbj(kind, f, Q)
+    x = _sig_dist(oracle_mod, C, dt, FR5, 2)
+    G, M = biquad_ref.biquad_gain(coef), biquad_ref.biquad_scale(x)
+    loop = biquad_ref.biquad_loop(x, coef, C)[0]
+    xt = torch.from_numpy(x.copy())
+    y = torch.from_numpy(loop.astype(np.float32))
+    W = biquad_lead(coef)
+    rho = biquad_ref.pole_radius(coef)
+    assert rho ** W <= 2.0 ** -70 < rho ** (W - 1)
+    for chunk in _chunks_for(W):
+        keep = torch.full((x.size,), float("nan"), dtype=torch.float64)
+        stats = {}
+        assert chunked_biquad_mismatches(xt, y, coef, C, G, M, chunk, stats=stats, keep=keep) == (0, None), chunk
+        dev = float(np.abs(keep.numpy() - loop).max()) / (G * M)
+        print(f"biquad {dt} C={C} {kind} f={f} Q={Q} chunk={chunk}: |ref - loop| <= {dev:.2e} G M, "
+              f"worst err / bar {stats['worst']:.3f}")
+        assert dev <= 2.0 ** -35, (chunk, dev)
+        assert 0.0 < stats["worst"] <= 1.0
+    ff = 12345
+    junk = y.clone()
+    junk[:ff * C] = 7.0
+    assert chunked_biquad_mismatches(xt, junk, coef, C, G, M, 3001, first_frame=ff) == (0, None)
+    assert chunked_biquad_mismatches(xt, _flip(junk, ff * C, 20), coef, C, G, M, 3001, first_frame=ff) == (1, ff * C)
+    _tamper_recursive(lambda t: chunked_biquad_mismatches(xt, t, coef, C, G, M, 3001), y)

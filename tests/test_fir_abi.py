@@ -54,7 +54,8 @@ def test_header_carries_the_contract():
     assert re.search(r"#define MAVG_ABI_VERSION 4\b", h)
     assert h.index("int mavg_biquad_plan") < h.index("FIR filter (finite impulse response)")   # after the biquad block
     block = h[h.index("FIR filter (finite impulse response)"):h.index("int mavg_fir_run")]
-    for word in ("bitwise", "2^-23", "2^-36", "oldest frame first", "16 KiB", "NOT tested past 2^31 samples",
+    assert "NOT tested past 2^31 samples" not in block
+    for word in ("bitwise", "2^-23", "2^-36", "oldest frame first", "16 KiB", "tests/test_gpu_bigsignal_filters.py",
                  "+0.0", "fma(h[j], (double)x[f-j], acc)", "never reads the taps on the host", "DEVICE memory"):
         assert word in block, word
     with open(os.path.join(ROOT, "include", "mavg_debug.h")) as f:

@@ -26,9 +26,15 @@ sliced, the oracle applied `passes` times, tests/stat_ref.py), guard bands
 around every output view (d_out and d_mean), the input checksum, and for the
 decimated output its exact length.
 
+The filters with kernels of their own -- extrema, EMA, biquad, FIR -- run the
+same signal through the same checks in tests/test_gpu_bigsignal_filters.py,
+which imports this file's helpers.
+
 A case holds 2 x 8.6 GB (int16) or 2 x 17.2 GB (fp32) plus < 5 GiB of chunk
 temporaries (the second moment: the input and two fp32 views, up to 3 x 17.2
-GB), and skips only when the (shared) device has less than that free."""
+GB; the filters' cases: an fp32 output per int16 input, 8.6 + 17.2 GB, and at
+most 3 x 17.2 GB for fp32 extrema with both outputs, plus up to 537 MB of
+records), and skips only when the (shared) device has less than that free."""
 import pytest
 
 from bigsignal_ref import chunked_mismatches
@@ -84,15 +90,16 @@ def _need(gpu, nbytes):
         pytest.skip(f"{free >> 30} GiB free on the device, this case needs {nbytes >> 30} GiB")
 
 
-def _stream(gpu, dtype, n, hs=0, in_off=0):
+def _stream(gpu, dtype, n, hs=0, in_off=0, dist=0):
     """Samples [0, hs + n) of the synthetic stream on the device: (xall, x, hist) with x = xall[hs:]
-    starting in_off samples past 16-B alignment and hist = xall[:hs] (None without one)."""
+    starting in_off samples past 16-B alignment and hist = xall[:hs] (None without one).  dist: the
+    generator's distribution (fp32 only: 0 int16-valued, 2 the rounding-stress data)."""
     import torch
     import digital_signal_processsing_amd as dsp
     esz = torch.empty(0, dtype=dtype).element_size()
     pad = (in_off - hs) % (16 // esz)
     xall = torch.empty(pad + hs + n, dtype=dtype, device=gpu)[pad:]
-    dsp.fill_synthetic(xall.numel(), seed=SEED, out=xall)
+    dsp.fill_synthetic(xall.numel(), seed=SEED, dist=dist, out=xall)
     x = xall[hs:]
     assert x.data_ptr() % 16 == (in_off * esz) % 16
     return xall, x, (xall[:hs] if hs else None)
@@ -350,12 +357,12 @@ def _out_windows(frames, centre, wf):
     return [(0, wf), (mid, mid + wf), (frames - wf, frames)]
 
 
-def _host_slice(oracle_mod, dt, C, f_lo, f_hi, lead):
+def _host_slice(oracle_mod, dt, C, f_lo, f_hi, lead, dist=0):
     """Stream frames [max(0, f_lo - lead), f_hi) regenerated on the host, and the frames in front of f_lo."""
     start = max(0, f_lo - lead)
     n = (f_hi - start) * C
     xs = oracle_mod.synth_i16(n, seed=SEED, offset=start * C) if dt == "i16" else \
-        oracle_mod.synth_f32(n, seed=SEED, offset=start * C, dist=0)
+        oracle_mod.synth_f32(n, seed=SEED, offset=start * C, dist=dist)
     return xs, f_lo - start
 
 
