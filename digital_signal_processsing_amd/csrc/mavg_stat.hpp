@@ -51,7 +51,27 @@ __device__ __forceinline__ double stat_i64_to_f64(int64_t s) {
 }
 
 // fp32 input: fp64 moments, the cancelling difference clamped at 0 (so is a mean square that
-// prefix differences left a rounding below 0), the root taken in fp32.
+// prefix differences left a rounding below 0).  The root: an fp32 mean square overflows from |x|
+// near 2^64 and underflows below 2^-75 although its root is an ordinary fp32 number, so the fp64
+// value v = w 4^h is split first, w in [0.5, 2) (the exponent field moved by an even number:
+// exact), w rounded to fp32, its correctly rounded fp32 root scaled by 2^h.  The same bits as
+// sqrtf((float)v) wherever (float)v is a normal number, and 4^e v gives exactly 2^e times the root
+// of v.  v == 0 (exponent field 0: h = -511) leaves as ldexpf(sqrt(0.5), -511) = 0.  (An fp64 root
+// rounded once, and this with frexp, ldexp and sqrtf, measured slower: DESIGN.md, Moments.)
+//
+// The correctly rounded fp32 root of w in [0.5, 2]: the hardware root is within one ulp, and the sign
+// of w - s * (neighbour of s), exact in one fma, says which neighbour is nearer -- sqrtf's own
+// correction, without its rescaling of subnormal input and its pass-through of 0 and Inf.
+__device__ __forceinline__ float stat_sqrt_half_2(float w) {
+  float s = __builtin_amdgcn_sqrtf(w);
+  const float down = __int_as_float(__float_as_int(s) - 1);
+  const float up = __int_as_float(__float_as_int(s) + 1);
+  const float rd = __builtin_fmaf(-down, s, w);
+  const float ru = __builtin_fmaf(-up, s, w);
+  s = rd <= 0.0f ? down : s;
+  s = ru > 0.0f ? up : s;
+  return s;
+}
 __device__ __forceinline__ float stat_value(double s1, double s2, const StatOut& o) {
   const double ms = s2 * o.inv_k;
   double v = ms;
@@ -59,9 +79,18 @@ __device__ __forceinline__ float stat_value(double s1, double s2, const StatOut&
     const double m = s1 * o.inv_k;
     v = ms - m * m;
   }
-  float y = (float)fmax(v, 0.0);
-  if (o.stat & 1) y = sqrtf(y);
-  return y;
+  v = fmax(v, 0.0);
+  const bool root = (o.stat & 1) != 0;
+  // the high word of v (sign 0) less that of 0.5: its bits from 21 up count the factors of 4 in
+  // v / 0.5, h (an arithmetic shift: floor), and the 21 below them, on 0.5's word, are v 4^-h
+  const int hi = __double2hiint(v);
+  const int t = hi - 0x3FE00000;
+  const int half = t >> 21;
+  // one conversion serves both: v, or v 4^-h for the root.  Selects, not a branch: the stat is
+  // uniform, but a branch at every output costs more than the root it skips.
+  const float f = (float)__hiloint2double(root ? ((t & 0x1FFFFF) | 0x3FE00000) : hi, __double2loint(v));
+  const float r = ldexpf(stat_sqrt_half_2(f), half);
+  return root ? r : f;
 }
 // int16 input: exact S1 and S2; N = k S2 - S1^2 exact in int64 while k <= 65535 (both products
 // below 2^62), else the moments in fp64.  The fp32 rounding of an fp64 evaluation.

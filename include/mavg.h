@@ -464,7 +464,12 @@ int mavg_cascade_plan(size_t n_samples, int channels, int grade, int passes, int
  * DC offset loses that much of its variance; remove the offset first (subtract
  * a constant, or this library's moving mean) when the variance is small beside
  * the squared mean.  The clamp at 0 is part of the contract: STD is never NaN
- * for finite input.  Nothing new is promised for non-finite input.
+ * for finite input.  RMS and STD take the root of the fp64 mean square or
+ * variance rescaled by an even power of two (rounded to fp32 there, the root in
+ * fp32, scaled back: all exact but the two roundings), so they are finite and
+ * hold their bars over the whole fp32 range of the input (|x| near 2^100 or
+ * 2^-110, subnormals); MEANSQ and VAR are +Inf when the true value exceeds
+ * FLT_MAX.  Nothing new is promised for non-finite input.
  *
  *   d_in       n_samples samples of `dtype`, sample-aligned.
  *   d_out      n_samples floats, 4-B aligned; must not overlap d_in.

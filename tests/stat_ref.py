@@ -99,8 +99,9 @@ def check_i16(y, ref, what=""):
 
 def check_f32(stat, y, ref, M, what=""):
     """The fp32 bars of include/mavg.h: 1e-5 relative for MEANSQ and RMS; VAR within 1e-5 of the
-    window's mean square M; STD: |y^2 - ref^2| <= 1e-5 M + 2^-22 ref^2 (the fp32 root of an fp32
-    variance), finite and >= 0."""
+    window's mean square M; STD: |y^2 - ref^2| <= 1e-5 M + 2^-22 ref^2 (VAR's bar on the square, plus
+    the roundings of the root: the fp32 root of the variance rounded to fp32 at a rescaled exponent,
+    1.5 * 2^-24 relative in all), finite and >= 0."""
     assert y.dtype == np.float32 and y.shape == ref.shape, (what, y.dtype, y.shape, ref.shape)
     y64 = y.astype(np.float64)
     if stat in (MEANSQ, RMS):

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Time the moving second moment against what callers compose today.
 
-    python tools/bench_stat.py [--steps 10] [--rounds 3] [--log2n 30] [--k 1024 ...] [--pairs] [--json out.json]
+    python tools/bench_stat.py [--steps 10] [--rounds 3] [--log2n 30] [--k 1024 ...] [--pairs] [--ab LIB LIB ...]
+                                [--json out.json]
 
 For every grade k, fp32 and int16, mono and stereo, 2^30 samples, and the variants MEANSQ (one
 scan), STD (two scans) and STD with d_mean, in ONE process on one device (lib/libmavg_hooks.so:
@@ -18,6 +19,10 @@ With --pairs, every shape additionally runs with stat_tile and stat_strip forced
 (mavg_debug_force_stat) where each can take it, at the grades whose halo k * C * sample size is
 256 B, 2 KiB, 8 KiB and 16 KiB: the pairs the tile rule is read from.  The strip is slow: use a
 smaller --log2n there.
+
+With --ab LIB [LIB ...], instead: mavg_stat_run alone (RMS, STD, STD with d_mean), by rule, through
+each of the given builds (make variant) in turn, the first the yardstick; give one build under two
+paths to read the spread.
 
 Times are means of one device-event pair per call (per composition for (b)), calls back to back.
 Rates are fractions of the 8 TB/s HBM peak over the ALGORITHMIC bytes of (a): n (s + 4), plus 4 n
@@ -139,6 +144,53 @@ def bench_shape(k, kind, variant, a, bufs, forced=()):
     return res
 
 
+AB_VARIANTS = (("rms", _lib.STAT_RMS, False), ("std", _lib.STAT_STD, False), ("std+mean", _lib.STAT_STD, True))
+
+
+def bench_ab(a):
+    """--ab: mavg_stat_run alone, by rule, through several builds of the library in one process
+    (each path its own handle; the same build under two paths gives the spread), after a warm-up of
+    every build, the rounds alternating the order.  Prints every build's mean and minimum and its
+    mean over the first build's."""
+    res = []
+    libs = [(p, _lib.load(p)) for p in a.ab]
+    stream = torch.cuda.current_stream().cuda_stream
+    for kind in a.dtypes:
+        tdt, C = KINDS[kind]
+        code = dsp.F32 if kind.startswith("f32") else dsp.I16
+        n = 1 << a.log2n
+        x = dsp.fill_synthetic(n, tdt, seed=0x5EED, dist=0, device="cuda")
+        y, mean = (torch.empty(n, dtype=torch.float32, device="cuda") for _ in range(2))
+        for k in a.k or [1024]:
+            for name, stat, with_mean in AB_VARIANTS:
+                mp = mean.data_ptr() if with_mean else None
+
+                def run(lib):
+                    _lib.check(lib.mavg_stat_run(x.data_ptr(), y.data_ptr(), mp, n, C, k, stat, code, None, stream), "mavg_stat_run")
+                for _, lib in libs:
+                    for _ in range(2):
+                        run(lib)
+                torch.cuda.synchronize()
+                t = {p: [] for p, _ in libs}
+                for r in range(a.rounds):
+                    for p, lib in (libs if r % 2 == 0 else libs[::-1]):
+                        t[p] += timed_launches(lambda: run(lib), a.steps)
+                ms = {p: statistics.mean(v) for p, v in t.items()}
+                first = ms[a.ab[0]]
+                nbytes = n * (x.element_size() + 4) + (4 * n if with_mean else 0)
+                print(f"{kind} k={k} {name}: {dsp.stat_plan(n, k, stat, C, code, with_mean, a.ab[0])}", flush=True)
+                for p, _ in libs:
+                    print(f"    {os.path.basename(p):28s} id {_lib.build_id(p)} mean {ms[p]:.4f} ms = {nbytes / (ms[p] * 1e-3) / PEAK:.4f} "
+                          f"of peak, min {min(t[p]):.4f} ms, mean / first = {ms[p] / first:.4f}", flush=True)
+                res.append({"dtype": kind, "channels": C, "k": k, "variant": name, "samples": n, "launches_timed": a.rounds * a.steps,
+                            "ms_mean": {os.path.basename(p): ms[p] for p, _ in libs},
+                            "ms_min": {os.path.basename(p): min(t[p]) for p, _ in libs},
+                            "over_first": {os.path.basename(p): ms[p] / first for p, _ in libs}})
+        del x, y, mean
+        torch.cuda.empty_cache()
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--steps", type=int, default=10, help="timed launches per round")
@@ -149,6 +201,8 @@ def main():
     ap.add_argument("--dtypes", nargs="+", default=list(KINDS), choices=list(KINDS))
     ap.add_argument("--variants", nargs="+", default=[v[0] for v in VARIANTS], choices=[v[0] for v in VARIANTS])
     ap.add_argument("--json", help="also write the results here")
+    ap.add_argument("--ab", nargs="+", metavar="LIB", help="time mavg_stat_run alone (RMS, STD, STD with d_mean) through these "
+                    "builds of the library against each other, the first the yardstick (make variant)")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("bench_stat.py needs the GPU (no CPU fallback)")
@@ -159,8 +213,8 @@ def main():
     del wake
     print(f"device {torch.cuda.get_device_name(0)}; libmavg_hooks build id {_lib.build_id(H)}; "
           f"rounds={a.rounds} steps={a.steps} samples=2^{a.log2n}", flush=True)
-    res = []
-    for kind in a.dtypes:
+    res = bench_ab(a) if a.ab else []
+    for kind in ([] if a.ab else a.dtypes):
         tdt, C = KINDS[kind]
         n = 1 << a.log2n
         x = dsp.fill_synthetic(n, tdt, seed=0x5EED, dist=0, device="cuda")
