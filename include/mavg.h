@@ -133,7 +133,21 @@ int mavg_workspace_bytes(size_t n_samples, int channels, int grade, int dtype,
  *     frames per thread: 2^33 or 2^34 frames.  Past it mavg_run and mavg_plan
  *     return MAVG_ERR_UNSUPPORTED and nothing is enqueued.
  * Every kernel family is tested on 2^32 + 10^6-sample signals
- * (tests/test_gpu_bigsignal.py).
+ * (tests/test_gpu_bigsignal.py).  The int16 kernels are tested at full scale --
+ * constant 32767 and -32768, window sums over the whole of [-32768 grade,
+ * 32767 grade] and on every quotient boundary of the output division -- on
+ * these paths (tests/test_gpu_i16_range.py): the eight explicit algorithms up
+ * to the largest grade each takes, the head-peel and frame-unit forms, the
+ * look-ahead scan with int32 and int64 sums up to grade 65537 (mono, stereo,
+ * the Hillis record carry; 4 channels at 44100 and 70000), wide_tile with 4
+ * and 8 channels, wide_ahead with 4 channels (4096 < grade <= 8192, int32 sums
+ * only: past it 4 channels take the look-ahead scan) and with 8 (int32 and
+ * int64), a d_history per kernel shape, and the rows, ragged, decimated and
+ * moment calls at their halo limits.  int16 has no chan_tile path.  NOT run at
+ * full scale: the window-matched and run-total forms of windows past the L2
+ * reach, 3, 5, 6 and 7 channels, and the cascade beyond its own
+ * test_int16_full_scale.  Both output divisions are modelled in
+ * tests/test_division.py.
  */
 int mavg_run(const void* d_in, void* d_out, size_t n_samples, int channels,
              int grade, int dtype, int algo, int block_size,
@@ -631,6 +645,9 @@ int mavg_extrema_plan(size_t n_samples, int channels, int grade, int dtype,
  * (the fp32 rounding, doubled; the truncation of ema_tile, at most 2^-30 M, and
  * fp64 re-association).  ema_chain and ema_strip do not truncate: their
  * d_state_out is within 1e-12 M of the reference; ema_tile's within 2^-29 M.
+ * The truncation is tested on its worst-case input, a constant M in front of a
+ * tile that starts past H, where nothing of the dropped tail cancels
+ * (tests/test_gpu_worst_case.py, tests/test_worst_case_model.py).
  * Nothing is promised for non-finite fp32 input.
  *
  * Ownership, stream and capture rules are mavg_run's: no allocation, no
@@ -751,7 +768,10 @@ int mavg_ema_plan(size_t n_samples, int channels, double alpha, int dtype, int f
  * below rests on an fp64 iteration whose rounding is ALLOWED 2^-32 G, an
  * allowance that is not derived (the iteration's error grows like n eps max
  * |u_n|) and is checked against the exact tail on a list of 80 filters and on
- * real-pole cases (tests/test_biquad_abi.py).  How it is formed: G is bounded below by the
+ * real-pole cases (tests/test_biquad_abi.py), and the kernels are run with it on
+ * the input that maximises what it drops, x[j] = M sgn(h[t0 - j]) in front of a
+ * tile that starts at t0 > H (tests/test_gpu_worst_case.py; DESIGN.md "Biquad"
+ * has the measured headroom).  How it is formed: G is bounded below by the
  * largest of |b0|, |h[1]| and the gains at DC and at Nyquist.  With u_m =
  * sum_j p1^j p2^(m-1-j) over the poles p1, p2 (|u_m| <= m rho^(m-1), rho the
  * larger modulus) the response is h[n] = c1 u_n + c2 u_(n-1), c1 = b1 - a1 b0,

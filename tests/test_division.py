@@ -73,3 +73,60 @@ def test_random_sums():
     s = rng.integers(-32768, 32768, k.size, dtype=np.int64) * k + rng.integers(-(2 ** 40), 2 ** 40, k.size) % k
     s = np.clip(s, -32768 * k, 32767 * k)
     assert np.array_equal(device_rule(s, k), exact_trunc(s, k))
+
+
+# ---- the magic multiply (dv=1 in the plan text): the default of the tile, segmented, decimated and cascade scans ----
+def magic_params(k):
+    """make_out_params (csrc/mavg_common.hip): l = ceil(log2 k), magic = floor(2^(31+l) / k) + 1,
+    shift = l - 1, for 2 <= k <= 65535, in uint64 (31 + l <= 47)."""
+    k = np.asarray(k, dtype=np.uint64)
+    l = np.ceil(np.log2(k.astype(np.float64))).astype(np.uint64)       # exact: k < 2^16, powers of two included
+    assert ((np.uint64(1) << l) >= k).all() and ((np.uint64(1) << (l - np.uint64(1))) < k).all()
+    magic = (np.uint64(1) << (np.uint64(31) + l)) // k + np.uint64(1)
+    return magic, l - np.uint64(1)
+
+
+def magic_rule(s, k):
+    """to_out_i16_magic (csrc/mavg_device.hpp): q = umulhi(|S|, magic) >> shift on uint32 operands,
+    then the sign of S.  |S| < 2^31 and magic < 2^32: the 64-bit product is exact in uint64."""
+    magic, shift = magic_params(k)
+    assert (magic < np.uint64(1) << np.uint64(32)).all()                 # the device keeps it in a uint32_t
+    a = np.abs(s).astype(np.uint64)
+    assert (a < np.uint64(1) << np.uint64(31)).all()
+    q = (((a * magic) >> np.uint64(32)) >> shift).astype(np.int64)
+    return np.where(s < 0, -q, q)
+
+
+@pytest.mark.parametrize("chunk", range(8))
+def test_magic_multiply_every_divisor(chunk):
+    """every k in [2, 65535], the 70 boundary sums each; the largest |S| is 32768 * 65535"""
+    ks = np.arange(max(2, 1 + chunk * 8192), min(65536, 1 + (chunk + 1) * 8192), dtype=np.int64)
+    s, kk = sums_at_boundaries(ks)
+    if chunk == 7:
+        assert np.abs(s).max() == 32768 * 65535 == 2147450880
+    got = magic_rule(s, kk)
+    want = exact_trunc(s, kk)
+    bad = np.argwhere(got != want)
+    assert bad.size == 0, f"first failure: S={s[tuple(bad[0])]} k={kk[tuple(bad[0])]}"
+    assert np.array_equal(got, device_rule(s, kk))                       # dv=0 and dv=1 are one function
+
+
+def test_magic_multiply_random_sums():
+    """the random sums of test_random_sums (same generator, same seed), restricted to k <= 65535"""
+    rng = np.random.default_rng(11)
+    k = rng.integers(1, 2 ** 31 - 1, 200000, dtype=np.int64)
+    k[:100000] = rng.integers(1, 65536, 100000)
+    s = rng.integers(-32768, 32768, k.size, dtype=np.int64) * k + rng.integers(-(2 ** 40), 2 ** 40, k.size) % k
+    s = np.clip(s, -32768 * k, 32767 * k)
+    sel = (k >= 2) & (k <= 65535)
+    assert sel.sum() >= 100000 - 100
+    assert np.array_equal(magic_rule(s[sel], k[sel]), exact_trunc(s[sel], k[sel]))
+
+
+def test_magic_without_its_plus_one_fails():
+    """The + 1 matters: floor(2^(31+l) / k) alone underestimates exact multiples (S = q k)."""
+    k = np.arange(2, 65536, dtype=np.int64)
+    s, kk = sums_at_boundaries(k)
+    magic, shift = magic_params(kk)
+    q = (((np.abs(s).astype(np.uint64) * (magic - np.uint64(1))) >> np.uint64(32)) >> shift).astype(np.int64)
+    assert (np.where(s < 0, -q, q) != exact_trunc(s, kk)).any()
