@@ -25,7 +25,7 @@ from __future__ import annotations
 from typing import Optional
 
 from . import _lib
-from ._lib import (ALGOS, F32, FIR_AUTO, FIR_STRIP, FIR_TILE, I16, STATS, MavgError, MavgLibraryError,  # noqa: F401
+from ._lib import (ALGOS, F32, FIR_AUTO, FIR_STRIP, FIR_TILE, I16, SOS_AUTO, SOS_LOOP, SOS_TILE, STATS, MavgError, MavgLibraryError,  # noqa: F401
                    algo_name, strerror)
 
 __all__ = [
@@ -73,6 +73,11 @@ __all__ = [
     "biquad_workspace_bytes",
     "biquad_halo_frames",
     "sos_filter",
+    "sosfilt",
+    "sosfilt_into",
+    "sos_plan",
+    "sos_workspace_bytes",
+    "sos_halo_frames",
     "fir_filter",
     "fir_filter_into",
     "fir_taps",
@@ -1123,7 +1128,8 @@ def sos_filter(x, sos, channels: int = 1, state=None, return_state: bool = False
     result.  THE INTERMEDIATE BETWEEN SECTIONS IS fp32 (one rounding per section, about ``2**-24``
     of the intermediate's size); a cascade that needs an fp64 intermediate is not this function.
     ``state``: a ``float64`` device tensor ``[S, channels, 2]`` (``sosfilt``'s ``zi`` with the
-    channel axis second); ``return_state``: return ``(y, state)`` of that shape."""
+    channel axis second); ``return_state``: return ``(y, state)`` of that shape.  ``sosfilt`` is
+    the cascade in one library call, with an fp64 intermediate wherever its fused kernel fits."""
     torch = _torch()
     rows = sos.tolist() if hasattr(sos, "tolist") else [list(r) for r in sos]
     if not rows or any(not hasattr(r, "__len__") or len(r) != 6 for r in rows):
@@ -1158,6 +1164,134 @@ def sos_filter(x, sos, channels: int = 1, state=None, return_state: bool = False
     out = _with_out(like, stream, into, (x, state), tuple(x.shape))
     if return_state and x.numel() == 0 and state is not None:
         sout[0].copy_(state)
+    return (out, sout[0]) if return_state else out
+
+
+def _sos_rows(sos):
+    """``sos`` -- a scipy ``[S, 6]`` array of ``(b0, b1, b2, a0, a1, a2)`` rows -- as ``(S, the S x 5
+    host doubles mavg_sos_run reads)``, every row normalised and checked by ``biquad_coef``."""
+    import ctypes
+    rows = sos.tolist() if hasattr(sos, "tolist") else [list(r) for r in sos]
+    if not rows or any(not hasattr(r, "__len__") or len(r) != 6 for r in rows):
+        raise ValueError("sos must be a non-empty [S, 6] array of (b0, b1, b2, a0, a1, a2) rows")
+    flat = [v for r in rows for v in biquad_coef(r)]
+    return len(rows), (ctypes.c_double * len(flat))(*flat)
+
+
+def _sos_flags(intermediate: str) -> int:
+    if intermediate not in ("auto", "fp64"):
+        raise ValueError(f"intermediate must be 'auto' or 'fp64', got {intermediate!r}")
+    return _lib.SOS_FP64_ONLY if intermediate == "fp64" else 0
+
+
+def sos_halo_frames(sos, library: Optional[str] = None) -> int:
+    """The sum of the sections' ``biquad_halo_frames``: how far back ``sos_tile`` stages."""
+    import ctypes
+    S, c = _sos_rows(sos)
+    out = ctypes.c_longlong(0)
+    _lib.check(_lib.load(library).mavg_sos_halo_frames(c, S, ctypes.byref(out)), "mavg_sos_halo_frames")
+    return out.value
+
+
+def sos_workspace_bytes(n: int, sos, channels: int = 1, dtype: int = F32, intermediate: str = "auto",
+                        library: Optional[str] = None) -> int:
+    """Device workspace ``sosfilt_into`` needs: the sections' tables for ``sos_tile``, one or two
+    fp32 buffers of the signal's size and the sections' own for ``sos_loop``."""
+    import ctypes
+    S, c = _sos_rows(sos)
+    out = ctypes.c_size_t(0)
+    _lib.check(_lib.load(library).mavg_sos_workspace_bytes(n, channels, c, S, dtype, _sos_flags(intermediate),
+                                                           ctypes.byref(out)), "mavg_sos_workspace_bytes")
+    return out.value
+
+
+def sos_plan(n: int, sos, channels: int = 1, dtype: int = F32, state: bool = False, return_state: bool = False,
+             intermediate: str = "auto", library: Optional[str] = None, aligned: bool = True) -> str:
+    """What mavg_sos_run would do (nothing is launched): ``sos_none biquad_...`` for one section,
+    ``sos_tile<...> sections=S intermediate=f64 ... tile_frames=N ... launches=1+S`` or ``sos_loop
+    ... intermediate=f32 ...``.  ``aligned=False``: for views off 16-B alignment (``F=1``)."""
+    import ctypes
+    S, c = _sos_rows(sos)
+    buf = ctypes.create_string_buffer(512)
+    flags = (_sos_flags(intermediate) | (_lib.SOS_PLAN_STATE_IN if state else 0)
+             | (_lib.SOS_PLAN_STATE_OUT if return_state else 0) | (0 if aligned else _lib.SOS_PLAN_UNALIGNED))
+    _lib.check(_lib.load(library).mavg_sos_plan(n, channels, c, S, dtype, flags, buf, len(buf)), "mavg_sos_plan")
+    return buf.value.decode()
+
+
+def _sos_state_ptr(state, S: int, C: int, what: str):
+    torch = _torch()
+    if state is None:
+        return None
+    if state.dtype != torch.float64 or state.numel() != S * C * 2 or not state.is_cuda or not state.is_contiguous():
+        raise ValueError(f"{what} must be a contiguous float64 device tensor of [sections, channels, 2] = "
+                         f"[{S}, {C}, 2] values")
+    return state.data_ptr()
+
+
+def sosfilt_into(x, out, sos, channels: int = 1, state=None, state_out=None, intermediate: str = "auto", stream=None,
+                 workspace=None, library: Optional[str] = None) -> None:
+    """Enqueue ``out = sosfilt(sos, x)`` on ``stream`` (default: current): one ``mavg_sos_run``.
+
+    ``out``: a contiguous ``float32`` device tensor of ``x``'s size that does not overlap ``x``.
+    ``state`` / ``state_out``: ``float64`` device tensors of ``[sections, channels, 2]`` values, not
+    the same tensor.  ``intermediate="fp64"`` raises (``MAVG_ERR_UNSUPPORTED``) where the library
+    would run the per-section loop with its fp32 intermediate.  ``workspace``: as in
+    ``biquad_into`` (``sos_workspace_bytes``)."""
+    torch = _torch()
+    S, c = _sos_rows(sos)
+    flags = _sos_flags(intermediate)
+    frames, C = _decim_shape(x, channels)
+    dt = _dtype_code(x)
+    if out.dtype != torch.float32:
+        raise ValueError(f"out must be float32 (the cascade is fp32 for every input dtype), got {out.dtype}")
+    if out.numel() != x.numel():
+        raise ValueError(f"out must hold x's {x.numel()} samples, got {out.numel()}")
+    _check_device_pair(x, out)
+    sin = _sos_state_ptr(state, S, C, "state")
+    sout = _sos_state_ptr(state_out, S, C, "state_out")
+    if sin is not None and sin == sout:
+        raise ValueError("state and state_out must not be the same tensor")
+    import ctypes
+    lib = _lib.load(library)
+    need = ctypes.c_size_t(0)
+    _lib.check(lib.mavg_sos_workspace_bytes(x.numel(), C, c, S, dt, flags, ctypes.byref(need)), "mavg_sos_workspace_bytes")
+    ws, ws_n = _loop_workspace(need.value, workspace, stream, x.device, "sos_workspace_bytes")
+    st = lib.mavg_sos_run(x.data_ptr(), out.data_ptr(), x.numel(), C, c, S, dt, flags, sin, sout,
+                          ws.data_ptr() if ws is not None else None, ws_n, _stream_handle(stream, x.device))
+    _lib.check(st, "mavg_sos_run")
+
+
+def sosfilt(x, sos, channels: int = 1, state=None, return_state: bool = False, intermediate: str = "auto", stream=None,
+            workspace=None, library: Optional[str] = None):
+    """``scipy.signal.sosfilt`` per channel of ``x`` (fp32 or int16), as ``float32`` in ``x``'s
+    shape, in one library call: ``sos`` is ``[S, 6]`` rows ``(b0, b1, b2, a0, a1, a2)``.  Where the
+    fused kernel fits (one or two channels, up to 16 sections, a total halo of at most 16 KiB of
+    fp64: ``sos_plan`` says ``sos_tile``) the intermediate between sections is fp64 and only the
+    result is rounded to fp32; elsewhere the library loops over the sections with an fp32
+    intermediate, as ``sos_filter`` does, and ``intermediate="fp64"`` raises instead.  ``state``: a
+    ``float64`` device tensor ``[S, channels, 2]`` (``sosfilt``'s ``zi`` with the channel axis
+    second); ``return_state``: return ``(y, state)`` of that shape."""
+    torch = _torch()
+    S, _ = _sos_rows(sos)
+    _sos_flags(intermediate)
+    _check_device_x(x)
+    _decim_shape(x, channels)
+    _dtype_code(x)
+    C = channels if x.dim() == 1 else x.shape[1]
+    _sos_state_ptr(state, S, C, "state")
+    like = x.new_empty(0, dtype=torch.float32)  # _with_out's model: x's device, float32
+    sout = []
+
+    def into(out):
+        if return_state:
+            sout.append(_on_stream(stream, lambda: torch.zeros((S, C, 2), dtype=torch.float64, device=x.device)))
+        sosfilt_into(x, out, sos, channels=C, state=state, state_out=sout[0] if sout else None,
+                     intermediate=intermediate, stream=stream, workspace=workspace, library=library)
+
+    out = _with_out(like, stream, into, (x, state), tuple(x.shape))
+    if return_state and x.numel() == 0 and state is not None:
+        sout[0].copy_(state.reshape(S, C, 2))
     return (out, sout[0]) if return_state else out
 
 

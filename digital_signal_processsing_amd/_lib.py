@@ -78,6 +78,10 @@ EXPORTED_SYMBOLS = (
     "mavg_biquad_workspace_bytes",
     "mavg_biquad_halo_frames",
     "mavg_biquad_plan",
+    "mavg_sos_run",
+    "mavg_sos_workspace_bytes",
+    "mavg_sos_halo_frames",
+    "mavg_sos_plan",
     "mavg_fir_run",
     "mavg_fir_plan",
     "mavg_resolve_algo",
@@ -92,7 +96,7 @@ EXPORTED_SYMBOLS = (
 # exported by the debug build only (include/mavg_debug.h)
 DEBUG_SYMBOLS = ("mavg_test_ahead_schedule", "mavg_debug_force_decim", "mavg_debug_force_cascade",
                  "mavg_debug_force_stat", "mavg_debug_force_extrema", "mavg_debug_force_ema",
-                 "mavg_debug_force_biquad", "mavg_debug_force_fir")
+                 "mavg_debug_force_biquad", "mavg_debug_force_fir", "mavg_debug_force_sos")
 # mavg_debug_force_decim's paths (include/mavg_debug.h)
 DECIM_AUTO, DECIM_SCAN, DECIM_WINDOW, DECIM_FULL = 0, 1, 2, 3
 # mavg_debug_force_cascade's paths (include/mavg_debug.h)
@@ -108,6 +112,10 @@ EXTREMA_AUTO, EXTREMA_TILE, EXTREMA_STRIP = 0, 1, 2
 EMA_AUTO, EMA_TILE, EMA_CHAIN, EMA_STRIP = 0, 1, 2, 3
 # mavg_debug_force_biquad's paths (include/mavg_debug.h)
 BIQUAD_AUTO, BIQUAD_TILE, BIQUAD_CHAIN, BIQUAD_STRIP = 0, 1, 2, 3
+# mavg_debug_force_sos's paths (include/mavg_debug.h); mavg_sos_run's flag and mavg_sos_plan's view bits
+SOS_AUTO, SOS_TILE, SOS_LOOP = 0, 1, 2
+SOS_FP64_ONLY = 1
+SOS_PLAN_STATE_IN, SOS_PLAN_STATE_OUT, SOS_PLAN_UNALIGNED = 16, 32, 64
 # mavg_debug_force_fir's paths (include/mavg_debug.h)
 FIR_AUTO, FIR_TILE, FIR_STRIP = 0, 1, 2
 ABI_VERSION = 4
@@ -219,6 +227,18 @@ def load(path: str = None) -> ctypes.CDLL:
     lib.mavg_biquad_halo_frames.restype = i
     lib.mavg_biquad_plan.argtypes = [sz, i, coef5, i, i, ctypes.c_char_p, sz]
     lib.mavg_biquad_plan.restype = i
+    dp = ctypes.POINTER(ctypes.c_double)
+    lib.mavg_sos_run.argtypes = [vp, vp, sz, i, dp, i, i, i, vp, vp, vp, sz, vp]
+    lib.mavg_sos_run.restype = i
+    lib.mavg_sos_workspace_bytes.argtypes = [sz, i, dp, i, i, i, ctypes.POINTER(sz)]
+    lib.mavg_sos_workspace_bytes.restype = i
+    lib.mavg_sos_halo_frames.argtypes = [dp, i, ctypes.POINTER(ctypes.c_longlong)]
+    lib.mavg_sos_halo_frames.restype = i
+    lib.mavg_sos_plan.argtypes = [sz, i, dp, i, i, i, ctypes.c_char_p, sz]
+    lib.mavg_sos_plan.restype = i
+    if hasattr(lib, "mavg_debug_force_sos"):  # debug and hooks builds only
+        lib.mavg_debug_force_sos.argtypes = [i]
+        lib.mavg_debug_force_sos.restype = i
     if hasattr(lib, "mavg_debug_force_biquad"):  # debug and hooks builds only
         lib.mavg_debug_force_biquad.argtypes = [i]
         lib.mavg_debug_force_biquad.restype = i

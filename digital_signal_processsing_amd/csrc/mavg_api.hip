@@ -12,6 +12,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
+#include <vector>
 
 #include "mavg_launch.hpp"
 
@@ -730,6 +731,128 @@ int biquad_launch(int path, const BiquadCall& a, Workspace ws, hipStream_t s) {
   return path == kBiquadTile ? biquad_tile_any(a.dtype, a.C, bs, s) : biquad_chain_any(a.dtype, a.C, bs, ws, s);
 }
 
+// ---- second-order sections (mavg_sos_run) -------------------------------------------------------
+constexpr long long kSosHaloSaturated = 1LL << 62;
+constexpr int kSosPlanShift = 4;  // mavg_sos_plan's flags: the view bits sit above the run flags
+constexpr int kSosMaxLoopSections = 1 << 20;
+constexpr long long kSosI16MonoPairHaloBytes = 2048;  // (sos_path)
+
+// the biquad's checks on every row
+int validate_sos(size_t n, int C, const double* coef, int sections, int dtype) {
+  const int st = validate(n, C, 1, dtype, MAVG_ALGO_AUTO, 0);
+  if (st != MAVG_OK) return st;
+  if (coef == nullptr || sections < 1) return MAVG_ERR_INVALID_ARG;
+  for (int j = 0; j < sections; ++j) {
+    const int sj = validate_biquad(n, C, coef + 5 * (size_t)j, dtype);
+    if (sj != MAVG_OK) return sj;
+  }
+  return MAVG_OK;
+}
+
+struct SosCall {
+  const void* in;
+  float* out;
+  const double* state_in;
+  double* state_out;
+  size_t n;
+  int C;
+  const double* coef;
+  int sections;
+  int dtype;
+  int flags;
+  std::vector<long long> halo;  // the rows' H
+  long long sum_halo;           // saturates at kSosHaloSaturated
+
+  void form_halos() {
+    halo.resize((size_t)sections);
+    sum_halo = 0;
+    for (int j = 0; j < sections; ++j) {
+      halo[(size_t)j] = biquad_halo_frames(coef + 5 * (size_t)j);
+      sum_halo = std::min(kSosHaloSaturated, sum_halo + std::min(halo[(size_t)j], kSosHaloSaturated));
+    }
+  }
+};
+
+// The dispatch rule for two or more sections, in the order mavg.h gives; *path = kSosTile /
+// kSosLoop.  The test hook's forced path replaces the rule; a forced sos_tile that cannot take the
+// shape, and MAVG_SOS_FP64_ONLY on a shape the fused kernel does not fit, are MAVG_ERR_UNSUPPORTED.
+int sos_path(const SosCall& a, int* path) {
+  const bool tile_ok = sos_tile_fits(a.C, a.sections, a.sum_halo);
+  // The one part of the fitted range where the fused kernel measured slower than the loop
+  // (tools/bench_sos.py --pairs, DESIGN.md "SOS"): int16 mono, two sections, 0.90x at 8 KiB and
+  // 0.86x at 16 KiB of total halo against 1.09x at 2 KiB.  The rule gives it to the loop past
+  // 2 KiB; MAVG_SOS_FP64_ONLY and the hook still reach the tile there.
+  const bool slower = a.dtype == MAVG_I16 && a.C == 1 && a.sections == 2 && a.sum_halo * 8 > kSosI16MonoPairHaloBytes;
+  const bool want_tile = tile_ok && (!slower || (a.flags & MAVG_SOS_FP64_ONLY) != 0);
+  int forced = kSosAuto;
+#ifdef MAVG_TEST_HOOKS
+  forced = g_test_sos_path.load(std::memory_order_relaxed);
+#endif
+  if (forced == kSosTile && !tile_ok) return MAVG_ERR_UNSUPPORTED;
+  *path = forced != kSosAuto ? forced : want_tile ? kSosTile : kSosLoop;
+  if (*path == kSosLoop && (a.flags & MAVG_SOS_FP64_ONLY) != 0) return MAVG_ERR_UNSUPPORTED;
+  if (*path == kSosLoop && a.sections > kSosMaxLoopSections) return MAVG_ERR_UNSUPPORTED;
+  return MAVG_OK;
+}
+
+int sos_tile_launch(const SosCall& a, Workspace ws, hipStream_t s) {
+  SosSig ss{a.in, a.out, a.state_in, a.state_out, a.n / (size_t)a.C, a.coef, a.sections, a.halo.data()};
+  ss.unit = aligned(a.in, 16) && aligned(a.out, 16);
+  ss.eio = !ss.unit && !aligned(a.in, elem_size(a.dtype) * (size_t)a.C) ? 1 : 0;
+  return sos_tile_any(a.dtype, a.C, ss, ws, s);
+}
+
+// sos_loop's workspace, in this order: one fp32 buffer of the signal's size (16-B padded), a second
+// one with three or more sections, then the largest workspace a section's mavg_biquad_run needs.
+struct SosLoopLayout {
+  size_t buf = 0, inner = 0;
+  int nbuf = 0;
+  int launches = 0;
+  size_t bytes() const { return (size_t)nbuf * buf + inner; }
+};
+
+// Section j of the loop as a biquad call: from d_in or the buffer section j - 1 wrote ((j - 1) & 1)
+// to the buffer j & 1 or d_out.  launch == false: every section is planned (its limits, its
+// workspace, its launches) with the buffers at `base`, nothing enqueued.
+int sos_loop(const SosCall& a, char* base, SosLoopLayout* L, hipStream_t s, bool launch) {
+  if (!launch) {
+    if (a.n > (SIZE_MAX / 4 - 64) / 2) return MAVG_ERR_UNSUPPORTED;  // the byte counts stay in size_t
+    L->buf = (a.n * 4 + 15) & ~(size_t)15;
+    L->nbuf = a.sections > 2 ? 2 : 1;
+    L->inner = 0;
+    L->launches = 0;
+  }
+  for (int j = 0; j < a.sections; ++j) {
+    const void* const in = j == 0 ? a.in : base + (size_t)((j - 1) & 1) * L->buf;
+    float* const out = j == a.sections - 1 ? a.out : reinterpret_cast<float*>(base + (size_t)(j & 1) * L->buf);
+    const int dtype = j == 0 ? a.dtype : MAVG_F32;
+    const size_t so = (size_t)j * (size_t)a.C * 2;
+    const BiquadCall c{in, out, a.state_in != nullptr ? a.state_in + so : nullptr,
+                       a.state_out != nullptr ? a.state_out + so : nullptr, a.n, a.C, a.coef + 5 * (size_t)j,
+                       a.halo[(size_t)j], dtype};
+    int path = kBiquadStrip;
+    int st = biquad_path(a.C, c.halo, dtype, &path);
+    if (st != MAVG_OK) return st;
+    if (launch) {
+      st = biquad_launch(path, c, Workspace{base + (size_t)L->nbuf * L->buf, L->inner}, s);
+      if (st != MAVG_OK) return st;
+      continue;
+    }
+    {
+      PlanScope ps;
+      st = biquad_launch(path, c, Workspace{}, nullptr);
+      if (st != MAVG_OK) return st;
+    }
+    size_t need = 0;
+    st = biquad_ws_bytes(path, c, &need);
+    if (st != MAVG_OK) return st;
+    L->inner = std::max(L->inner, need);
+    L->launches += path == kBiquadTile ? 1 : 3;
+  }
+  if (!launch && L->inner > SIZE_MAX - (size_t)L->nbuf * L->buf) return MAVG_ERR_UNSUPPORTED;
+  return MAVG_OK;
+}
+
 // cascade_loop's workspace, in this order: the ping-pong buffer (the signal's bytes, 16-B padded);
 // with a history two block buffers of passes * (grade - 1) * C samples each (16-B padded); then
 // mavg_run's own workspace -- the signal's, and with a history at least the first block's.
@@ -1359,6 +1482,125 @@ int mavg_biquad_run(const void* d_in, float* d_out, size_t n_samples, int channe
   st = check_workspace(need, d_ws, ws_bytes);
   if (st != MAVG_OK) return st;
   return biquad_launch(path, a, Workspace{d_ws, ws_bytes}, static_cast<hipStream_t>(stream));
+}
+
+int mavg_sos_halo_frames(const double* coef, int sections, long long* out_frames) {
+  if (out_frames == nullptr) return MAVG_ERR_INVALID_ARG;
+  const int st = validate_sos(0, 1, coef, sections, MAVG_F32);
+  if (st != MAVG_OK) return st;
+  SosCall a{nullptr, nullptr, nullptr, nullptr, 0, 1, coef, sections, MAVG_F32, 0, {}, 0};
+  a.form_halos();
+  *out_frames = a.sum_halo;
+  return MAVG_OK;
+}
+
+int mavg_sos_workspace_bytes(size_t n_samples, int channels, const double* coef, int sections, int dtype, int flags,
+                             size_t* out_bytes) {
+  if (out_bytes == nullptr) return MAVG_ERR_INVALID_ARG;
+  int st = validate_sos(n_samples, channels, coef, sections, dtype);
+  if (st != MAVG_OK) return st;
+  if (flags < 0 || (flags & ~MAVG_SOS_FP64_ONLY) != 0) return MAVG_ERR_INVALID_ARG;
+  if (sections == 1) return mavg_biquad_workspace_bytes(n_samples, channels, coef, dtype, out_bytes);
+  *out_bytes = 0;
+  if (n_samples == 0) return MAVG_OK;
+  SosCall a{kPlanIn, static_cast<float*>(kPlanOut), nullptr, nullptr, n_samples, channels, coef, sections, dtype, flags, {}, 0};
+  a.form_halos();
+  int path = kSosLoop;
+  st = sos_path(a, &path);
+  if (st != MAVG_OK) return st;
+  if (path == kSosTile) {
+    PlanScope ps;  // the launch's own limit (grid_too_large) shows here as it does in mavg_sos_run
+    st = sos_tile_launch(a, Workspace{}, nullptr);
+    if (st == MAVG_OK) *out_bytes = sos_tile_ws_bytes(sections);
+    return st;
+  }
+  SosLoopLayout L;
+  st = sos_loop(a, static_cast<char*>(const_cast<void*>(kPlanOff)), &L, nullptr, false);
+  if (st == MAVG_OK) *out_bytes = L.bytes();
+  return st;
+}
+
+int mavg_sos_plan(size_t n_samples, int channels, const double* coef, int sections, int dtype, int flags, char* buf,
+                  size_t buflen) {
+  if (buf == nullptr || buflen == 0) return MAVG_ERR_INVALID_ARG;
+  buf[0] = 0;
+  int st = validate_sos(n_samples, channels, coef, sections, dtype);
+  if (st != MAVG_OK) return st;
+  const int views = flags >> kSosPlanShift;  // 1 / 2 / 4 as mavg_biquad_plan's
+  if (flags < 0 || views > 7 || (flags & ((1 << kSosPlanShift) - 1) & ~MAVG_SOS_FP64_ONLY) != 0) return MAVG_ERR_INVALID_ARG;
+  if (n_samples == 0) return MAVG_ERR_INVALID_ARG;  // nothing to describe, as mavg_plan
+  if (sections == 1) {
+    char inner[256];
+    st = mavg_biquad_plan(n_samples, channels, coef, dtype, views, inner, sizeof(inner));
+    if (st == MAVG_OK) snprintf(buf, buflen, "sos_none %s", inner);
+    return st;
+  }
+  // (view bit 4: views off 16-B alignment -- an input one sample past a 16-B boundary)
+  const void* const in = (views & 4) != 0 ? static_cast<const char*>(kPlanIn) + elem_size(dtype) : kPlanIn;
+  const double* const sin = (views & 1) != 0 ? static_cast<const double*>(kPlanOff) : nullptr;
+  double* const sout = (views & 2) != 0 ? static_cast<double*>(const_cast<void*>(kPlanOff)) + 64 : nullptr;
+  SosCall a{in, static_cast<float*>(kPlanOut), sin, sout, n_samples, channels, coef, sections, dtype,
+            flags & MAVG_SOS_FP64_ONLY, {}, 0};
+  a.form_halos();
+  int path = kSosLoop;
+  st = sos_path(a, &path);
+  if (st != MAVG_OK) return st;
+  if (path == kSosTile) {
+    PlanScope ps;
+    st = sos_tile_launch(a, Workspace{}, nullptr);
+    if (st == MAVG_OK) snprintf(buf, buflen, "%s", ps.plan.text);
+    return st;
+  }
+  SosLoopLayout L;
+  st = sos_loop(a, static_cast<char*>(const_cast<void*>(kPlanOff)) + 4096, &L, nullptr, false);
+  if (st == MAVG_OK)
+    snprintf(buf, buflen,
+             "sos_loop dtype=%s C=%d sections=%d intermediate=f32 halo_frames=%lld state=%d frames=%zu buffers=%d ws=%zu "
+             "launches=%d",
+             dtype == MAVG_F32 ? "f32" : "i16", channels, sections, a.sum_halo, views & 3, n_samples / (size_t)channels,
+             L.nbuf, L.bytes(), L.launches);
+  return st;
+}
+
+// sections == 1 (sos_none): mavg_biquad_run.  Else the fused tile kernel where the rule (sos_path)
+// takes the cascade, else one mavg_biquad_run per section through fp32 buffers in the workspace;
+// every launch is planned before the first is made.
+int mavg_sos_run(const void* d_in, float* d_out, size_t n_samples, int channels, const double* coef, int sections,
+                 int dtype, int flags, const double* d_state_in, double* d_state_out, void* d_ws, size_t ws_bytes,
+                 void* stream) {
+  int st = validate_sos(n_samples, channels, coef, sections, dtype);
+  if (st != MAVG_OK) return st;
+  if (flags < 0 || (flags & ~MAVG_SOS_FP64_ONLY) != 0) return MAVG_ERR_INVALID_ARG;
+  if (sections == 1)
+    return mavg_biquad_run(d_in, d_out, n_samples, channels, coef, dtype, d_state_in, d_state_out, d_ws, ws_bytes, stream);
+  if (d_state_in != nullptr && d_state_in == d_state_out) return MAVG_ERR_INVALID_ARG;
+  if (n_samples == 0) return MAVG_OK;
+  if (d_in == nullptr || d_out == nullptr) return MAVG_ERR_INVALID_ARG;
+  if (!aligned(d_in, elem_size(dtype)) || !aligned(d_out, 4) || !aligned(d_state_in, 8) || !aligned(d_state_out, 8))
+    return MAVG_ERR_MISALIGNED;
+  SosCall a{d_in, d_out, d_state_in, d_state_out, n_samples, channels, coef, sections, dtype, flags, {}, 0};
+  a.form_halos();
+  int path = kSosLoop;
+  st = sos_path(a, &path);
+  if (st != MAVG_OK) return st;
+  hipStream_t const s = static_cast<hipStream_t>(stream);
+  if (path == kSosTile) {
+    {
+      PlanScope ps;  // the launch's limits, with nothing enqueued
+      st = sos_tile_launch(a, Workspace{}, nullptr);
+      if (st != MAVG_OK) return st;
+    }
+    st = check_workspace(sos_tile_ws_bytes(sections), d_ws, ws_bytes);
+    if (st != MAVG_OK) return st;
+    return sos_tile_launch(a, Workspace{d_ws, ws_bytes}, s);
+  }
+  SosLoopLayout L;
+  // planned with the buffers at a 16-B aligned stand-in: the workspace's own alignment is checked below
+  st = sos_loop(a, static_cast<char*>(const_cast<void*>(kPlanOff)) + 4096, &L, nullptr, false);
+  if (st != MAVG_OK) return st;
+  st = check_workspace(L.bytes(), d_ws, ws_bytes);
+  if (st != MAVG_OK) return st;
+  return sos_loop(a, static_cast<char*>(d_ws), &L, s, true);
 }
 
 int mavg_fir_plan(size_t n_samples, int channels, int ntaps, int dtype, int flags, char* buf, size_t buflen) {

@@ -412,6 +412,11 @@ int biquad_strip_any(int dtype, int C, const BiquadSig& bs, Workspace ws, hipStr
   return dtype == MAVG_F32 ? launch_biquad_strip<float>(C, bs, ws, st) : launch_biquad_strip<int16_t>(C, bs, ws, st);
 }
 
+// the fused cascade's tables (mavg_sos.hip) take their powers and state horizon from here
+Mat2 biquad_mat_pow(const double coef[5], unsigned long long m) { return mat_pow(coef, m); }
+void biquad_fill_pow63(const double coef[5], unsigned long long m, MatPow<63>* t) { fill_level(coef, m, t); }
+long long biquad_state_horizon(const double coef[5]) { return biquad_state_frames(coef); }
+
 int biquad_chain_ws_bytes(size_t nframes, int C, size_t* bytes) { return records_bytes(nframes, kBiquadFrameTF, C, bytes); }
 int biquad_strip_ws_bytes(size_t nframes, int C, size_t* bytes) { return records_bytes(nframes, kBiquadStripFrames, C, bytes); }
 

@@ -15,6 +15,7 @@ std::atomic<int> g_test_extrema_path{kExtremaAuto};
 std::atomic<int> g_test_ema_path{kEmaAuto};
 std::atomic<int> g_test_biquad_path{kBiquadAuto};
 std::atomic<int> g_test_fir_path{kFirAuto};
+std::atomic<int> g_test_sos_path{kSosAuto};
 #endif
 
 // ---- per-device attribute cache (no stream work, capture-safe) --------------
@@ -88,6 +89,11 @@ extern "C" int mavg_debug_force_biquad(int path) {
 extern "C" int mavg_debug_force_fir(int path) {
   if (path < mavg::kFirAuto || path > mavg::kFirStrip) return MAVG_ERR_INVALID_ARG;
   mavg::g_test_fir_path.store(path, std::memory_order_relaxed);
+  return MAVG_OK;
+}
+extern "C" int mavg_debug_force_sos(int path) {
+  if (path < mavg::kSosAuto || path > mavg::kSosLoop) return MAVG_ERR_INVALID_ARG;
+  mavg::g_test_sos_path.store(path, std::memory_order_relaxed);
   return MAVG_OK;
 }
 #endif

@@ -389,6 +389,39 @@ int biquad_strip_any(int dtype, int C, const BiquadSig& bs, Workspace ws, hipStr
 int biquad_chain_ws_bytes(size_t nframes, int C, size_t* bytes);
 int biquad_strip_ws_bytes(size_t nframes, int C, size_t* bytes);
 
+// The fused cascade (mavg_sos.hpp, instantiated in mavg_sos.hip): `sections` biquads in series, the
+// intermediate fp64 in LDS, fp32 out; coef: sections x 5 (validated rows), halo: the rows'
+// biquad_halo_frames; state_in / state_out: [sections][C][2] doubles in device memory or NULL.
+//   unit  the 16-B-unit form (in and out 16-B aligned); else the frame-unit (F = 1) form
+//   eio   frame-unit form on an input that is only element-aligned (UnitIO::gload)
+struct SosSig {
+  const void* in;
+  float* out;
+  const double* state_in;
+  double* state_out;
+  size_t nframes;
+  const double* coef;
+  int sections;
+  const long long* halo;
+  bool unit = true;
+  int eio = 0;
+};
+// The test hook's forced path (mavg_debug_force_sos, include/mavg_debug.h): 0 = the rule decides
+constexpr int kSosAuto = 0, kSosTile = 1, kSosLoop = 2;
+#ifdef MAVG_TEST_HOOKS
+extern std::atomic<int> g_test_sos_path;
+#endif
+// Whether the fused kernel takes the cascade (the dispatch rule, and what a forced sos_tile may
+// run): channels 1 or 2, 2 .. kSosMaxSections sections, a total halo sum_halo * C * 8 B of at most
+// 16 KiB, and its LDS layout (SosLds, the same in both unit forms) inside lds_budget.
+bool sos_tile_fits(int C, int sections, long long sum_halo);
+// the sections' tables: what mavg_sos_workspace_bytes returns for sos_tile
+size_t sos_tile_ws_bytes(int sections);
+// One set-up launch per section and the filtering launch.  MAVG_ERR_UNSUPPORTED: the cascade does
+// not fit, or the launch would exceed grid_too_large; MAVG_ERR_WORKSPACE / MAVG_ERR_MISALIGNED for
+// the workspace.
+int sos_tile_any(int dtype, int C, const SosSig& ss, Workspace ws, hipStream_t st);
+
 // The FIR filter (mavg_fir.hpp, instantiated in mavg_fir.hip): y[f] = sum_j taps[j] x[f-j], one
 // fp64 fma chain per output, fp32 out, one launch; taps: ntaps doubles in device memory; hist holds
 // ntaps - 1 frames or is NULL.

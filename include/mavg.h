@@ -888,6 +888,130 @@ int mavg_biquad_halo_frames(const double coef[5], long long* out_frames);
 int mavg_biquad_plan(size_t n_samples, int channels, const double coef[5], int dtype, int flags,
                      char* buf, size_t buflen);
 
+/* Second-order sections: `sections` biquads in series, per channel of an
+ * interleaved signal -- scipy.signal.sosfilt with normalised rows.  coef holds
+ * sections x 5 host doubles, row j = b0 b1 b2 a1 a2 of section j (a0 == 1).
+ * Section j is mavg_biquad_run's recurrence (transposed direct form II, the
+ * states are lfilter's zi / zf); section j + 1 reads section j's output.  The
+ * input is MAVG_F32 or MAVG_I16, the output ALWAYS fp32, n_samples floats in
+ * d_in's layout; it must not overlap d_in.
+ *
+ * The intermediate.  On sos_tile (below) section j + 1 reads section j's output
+ * as fp64 and only the last section's output is rounded, once, to fp32: one
+ * fp64 pipeline from x to y.  On sos_loop THE INTERMEDIATE IS fp32 -- it is
+ * mavg_biquad_run once per section through fp32 buffers.  flags =
+ * MAVG_SOS_FP64_ONLY refuses, with MAVG_ERR_UNSUPPORTED and nothing enqueued,
+ * every shape that would not run with fp64 intermediates, so a caller who
+ * needs the fp64 contract never gets fp32 silently.
+ *
+ * State.  d_state_in / d_state_out hold [sections][channels][2] doubles in
+ * device memory, 8-B aligned, or are NULL (zeros / not wanted): row j is
+ * section j's (s1, s2) as mavg_biquad_run's.  They must not be equal.  Chunk
+ * i's state_out as chunk i + 1's state_in reproduces the one-shot output
+ * within the bars below, not bitwise.  mavg_biquad_run's "Which states"
+ * paragraph carries over section by section: a state the cascade can reach
+ * (NULL, an earlier call's d_state_out) is promised; any other state is applied
+ * on sos_tile only while its section's pole envelope falls to 2^-30 G within
+ * the 16 tiles after the first.
+ *
+ * Accuracy.  G_j is section j's sum |h|; m_1 = max(max |x|, |state_in[1]|),
+ * m_(j+1) = max(G_j m_j, |state_in[j+1]|); y_ref is the serial fp64 cascade
+ * with fp64 intermediates.  On sos_tile (and sos_none) every output satisfies
+ *
+ *   |y - y_ref| <= 2^-23 |y_ref| + 2^-29 sum_j ( G_j m_j prod_{i>j} G_i )
+ *
+ * -- each section's 2^-29 G M pushed through the gains of the sections after
+ * it -- while every section meets the biquad's D >= 2^-22; component c of
+ * d_state_out[j] is within the same sum taken over the sections <= j (without
+ * the later gains' product past j).  On sos_loop, a separate and weaker bar:
+ * each section before the last also rounds its output to fp32, which adds
+ *
+ *   2^-24 sum_{j < S} ( G_j m_j prod_{i>j} G_i )
+ *
+ * to the right-hand side (and to the states of the sections after it).
+ *
+ * Dispatch, evaluated in this order (mavg_sos_plan shows which):
+ *   sos_none  sections == 1: mavg_biquad_run unchanged, with its workspace.
+ *   sos_tile  channels 1 or 2, 2 <= sections <= 16, and a total halo sum_j H_j
+ *             (H_j = mavg_biquad_halo_frames of row j; mavg_sos_halo_frames) with
+ *             sum H_j * channels * 8 B <= 16 KiB: the stage limit of every tile
+ *             kernel here, taken in the intermediate's dtype.  ONE filtering
+ *             launch: a tile stages its 4096 / channels frames and the sum H_j
+ *             frames before them as fp64 in LDS (zeros before frame 0); section
+ *             j runs in place over the range that starts sum_{i>=j} H_i frames
+ *             before the tile, from a zero state (from d_state_in[j] exactly
+ *             where the range is cut at frame 0), and its first H_j outputs are
+ *             not used.  The sections' power tables (2712 B each, formed on the
+ *             host in long double and rounded once) travel as the kernel
+ *             arguments of one tiny set-up launch per section that writes them
+ *             to the workspace: launches = 1 + sections in the plan text.  The
+ *             16-B-unit form runs when d_in and d_out are 16-B aligned, the
+ *             frame-unit form (F=1) otherwise.  The rule is "wherever it fits"
+ *             but for one measured exception (tools/bench_sos.py --pairs, 2^28
+ *             samples, DESIGN.md "SOS"): forced against sos_loop it is 1.03x to
+ *             2.21x faster at 2, 4 and 8 sections and 256 B, 2, 8 and 16 KiB of
+ *             total halo, except int16 mono with TWO sections, 1.09x at 2 KiB but
+ *             0.90x at 8 KiB and 0.86x at 16 KiB.  There -- MAVG_I16, one channel,
+ *             two sections, sum H_j * 8 B > 2 KiB -- the rule gives the cascade
+ *             to sos_loop, and MAVG_SOS_FP64_ONLY (and the hook) still run it on
+ *             sos_tile.  Three sections and 3 .. 7 between the measured counts
+ *             were NOT MEASURED.
+ *   sos_loop  everything else -- three or more channels, longer total halos,
+ *             more sections: mavg_biquad_run's launches once per section on
+ *             `stream`, every section planned before the first is launched, the
+ *             last landing in d_out.  fp32 intermediate; refused by
+ *             MAVG_SOS_FP64_ONLY.
+ *
+ * Workspace (mavg_sos_workspace_bytes): sos_none mavg_biquad_run's; sos_tile
+ * sections * 2712 B rounded up to 16; sos_loop one fp32 buffer of the signal's
+ * size (two with three or more sections), each padded to 16 B, and the largest
+ * workspace a section's mavg_biquad_run needs.  d_ws 16-B aligned.  It needs no
+ * initialisation, so a call captures into a graph with no memset node.
+ *
+ * Ownership, stream, capture, "planned before anything is launched", "nothing
+ * enqueued unless MAVG_OK" and the n_samples == 0 rule are mavg_biquad_run's.
+ * Status: mavg_biquad_run's table with every row of coef checked as its coef is,
+ * and: sections < 1, or flags other than 0 / MAVG_SOS_FP64_ONLY, is
+ * MAVG_ERR_INVALID_ARG; MAVG_ERR_UNSUPPORTED for MAVG_SOS_FP64_ONLY on a shape
+ * sos_tile does not fit (more than 16 sections among them: the loop itself
+ * takes any count) and past mavg_biquad_run's one-launch limit.
+ *
+ * Supported maximum.  Frame and sample indices are 64-bit wherever they are not
+ * tile-local.  sos_tile is NOT yet tested past 2^32 samples.
+ */
+#define MAVG_SOS_FP64_ONLY 1
+int mavg_sos_run(const void* d_in, float* d_out, size_t n_samples, int channels,
+                 const double* coef /* host: sections x 5, rows b0 b1 b2 a1 a2, a0 == 1 */, int sections,
+                 int dtype, int flags,
+                 const double* d_state_in /* device [sections][channels][2] or NULL */,
+                 double* d_state_out /* same shape or NULL */,
+                 void* d_ws, size_t ws_bytes, void* stream);
+
+/* Device workspace mavg_sos_run needs for these arguments (see "Workspace"
+ * above); the argument checks and refusals are mavg_sos_run's. */
+int mavg_sos_workspace_bytes(size_t n_samples, int channels, const double* coef, int sections,
+                             int dtype, int flags, size_t* out_bytes);
+
+/* The sum of the rows' mavg_biquad_halo_frames (saturating at 2^62). */
+int mavg_sos_halo_frames(const double* coef, int sections, long long* out_frames);
+
+/* Describe, without launching anything, what mavg_sos_run would do:
+ * "sos_none biquad_...", "sos_tile<dtype,C=..,F=..> sections=S intermediate=f64
+ * halo_frames=H stage_halo=Hp state=0|1|2|3 frames=.. grid=.. block=.. lds=..
+ * tile_frames=N remap=.. ws=B launches=1+S" or "sos_loop dtype=.. C=.. sections=S
+ * intermediate=f32 halo_frames=H state=.. frames=.. buffers=1|2 ws=B launches=L".
+ * flags packs two things, in separate bit ranges: bits 0 .. 3 are mavg_sos_run's
+ * flags (MAVG_SOS_FP64_ONLY), bits 4 .. 6 describe the views as
+ * mavg_biquad_plan's 1 / 2 / 4 do, shifted left by four:
+ * MAVG_SOS_PLAN_STATE_IN, MAVG_SOS_PLAN_STATE_OUT and MAVG_SOS_PLAN_UNALIGNED
+ * (views off 16-B alignment: the frame-unit form).  n_samples == 0 has no plan:
+ * MAVG_ERR_INVALID_ARG. */
+#define MAVG_SOS_PLAN_STATE_IN 16
+#define MAVG_SOS_PLAN_STATE_OUT 32
+#define MAVG_SOS_PLAN_UNALIGNED 64
+int mavg_sos_plan(size_t n_samples, int channels, const double* coef, int sections, int dtype,
+                  int flags, char* buf, size_t buflen);
+
 /* FIR filter (finite impulse response), per channel of an interleaved signal
  * x[f*channels + c] with the caller's taps h[0 .. ntaps-1]:
  *

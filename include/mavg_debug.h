@@ -91,6 +91,17 @@ int mavg_debug_force_ema(int path);
  * MAVG_OK, or MAVG_ERR_INVALID_ARG for another value (nothing changes). */
 int mavg_debug_force_biquad(int path);
 
+/* TEST HOOK (parity tests and tools/bench_sos.py): force mavg_sos_run's path for
+ * two or more sections -- 0: the dispatch rule decides (the default),
+ * 1: sos_tile, 2: sos_loop -- with the semantics of mavg_debug_force_biquad: a
+ * forced sos_tile that cannot take the shape (three or more channels, more than
+ * 16 sections, a total halo past 16 KiB of fp64) makes mavg_sos_run,
+ * mavg_sos_plan and mavg_sos_workspace_bytes return MAVG_ERR_UNSUPPORTED; the
+ * workspace query follows the forced path; the loop takes every shape but is
+ * still refused by MAVG_SOS_FP64_ONLY.  Process-wide; returns MAVG_OK, or
+ * MAVG_ERR_INVALID_ARG for another value (nothing changes). */
+int mavg_debug_force_sos(int path);
+
 /* TEST HOOK (parity tests and tools/bench_fir.py): force mavg_fir_run's path --
  * 0: the dispatch rule decides (the default), 1: fir_tile, 2: fir_strip -- with
  * the semantics of mavg_debug_force_extrema: a forced fir_tile that cannot take

@@ -1,0 +1,360 @@
+"""The cascade's contract (mavg_sos_run, mavg_sos_workspace_bytes, mavg_sos_halo_frames,
+mavg_sos_plan in include/mavg.h; the hook mavg_debug_force_sos in include/mavg_debug.h): the symbols
+and ctypes signatures, the status table with dummy pointers, sos_none against the biquad's plan, both
+sides of every dispatch boundary as the plan text shows it, the forced paths, MAVG_SOS_FP64_ONLY,
+workspace sizes, the LDS layout at the boundary and the kernels' resource report.  No GPU.
+
+The rule: sos_none for one section; sos_tile for one or two channels, 2 .. 16 sections and a total
+halo sum H_j * channels * 8 B of at most 16 KiB (2048 frames mono, 1024 stereo, whatever the input
+dtype: the stage is fp64); sos_loop for everything else.  Measured boundary (DESIGN.md "SOS"): the
+fused kernel is 1.03x to 2.21x faster than the forced loop over the fitted range except int16 mono
+with two sections (1.09x at 2 KiB of total halo, 0.90x at 8 KiB, 0.86x at 16 KiB), which the
+default rule gives to sos_loop past 2 KiB (256 frames); MAVG_SOS_FP64_ONLY and the hook still run
+it fused."""
+import ctypes
+import os
+import re
+import subprocess
+import sys
+
+import pytest
+
+import digital_signal_processsing_amd as dsp
+from digital_signal_processsing_amd import _lib
+
+from sos_ref import HP_PK, SEVEN, THREE, butter4_lp, flat5, one_pole, rows6, sections_with_halo
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "digital_signal_processsing_amd", "csrc")
+SYMBOLS = ("mavg_sos_run", "mavg_sos_workspace_bytes", "mavg_sos_halo_frames", "mavg_sos_plan")
+HOOK = "mavg_debug_force_sos"
+F32, I16 = _lib.F32, _lib.I16
+NAME = {F32: "f32", I16: "i16"}
+MAX_SECTIONS = 16
+SECTION_BYTES = 2712                       # sizeof(SosSection): 40 + 16 + 63 * 32 + 4 * 32 + 16 * 32
+LIMIT = {1: 2048, 2: 1024}                 # frames of total halo sos_tile takes
+TILE_FRAMES = {1: 4096, 2: 2048}
+B4 = butter4_lp(0.05)
+COPY5 = (1.0, 0.0, 0.0, 0.0, 0.0)
+
+
+def coefs(sos):
+    flat = flat5(sos)
+    return (ctypes.c_double * len(flat))(*flat)
+
+
+def test_symbols_are_exported_by_every_build_and_the_hook_only_by_debug_and_hooks():
+    for path in (_lib.LIB_PATH, _lib.DEBUG_LIB_PATH, _lib.HOOKS_LIB_PATH):
+        lib = _lib.load(path)
+        for name in SYMBOLS:
+            assert hasattr(lib, name), (path, name)
+        assert lib.mavg_abi_version() == _lib.ABI_VERSION == 4  # additive: the version stays
+    assert set(SYMBOLS) <= set(_lib.EXPORTED_SYMBOLS)
+    assert not hasattr(_lib.load(), HOOK)                       # the release build has no hook
+    assert hasattr(_lib.load(_lib.DEBUG_LIB_PATH), HOOK) and HOOK in _lib.DEBUG_SYMBOLS
+    assert hasattr(_lib.load(_lib.HOOKS_LIB_PATH), HOOK)
+    assert (_lib.SOS_AUTO, _lib.SOS_TILE, _lib.SOS_LOOP) == (0, 1, 2) == (dsp.SOS_AUTO, dsp.SOS_TILE, dsp.SOS_LOOP)
+    assert _lib.SOS_FP64_ONLY == 1
+    assert (_lib.SOS_PLAN_STATE_IN, _lib.SOS_PLAN_STATE_OUT, _lib.SOS_PLAN_UNALIGNED) == (16, 32, 64)
+    lib = _lib.load()
+    assert len(lib.mavg_sos_run.argtypes) == 13
+    assert len(lib.mavg_sos_workspace_bytes.argtypes) == 7
+    assert len(lib.mavg_sos_halo_frames.argtypes) == 3
+    assert len(lib.mavg_sos_plan.argtypes) == 8
+    for fn in (dsp.sosfilt, dsp.sosfilt_into, dsp.sos_plan, dsp.sos_workspace_bytes, dsp.sos_halo_frames):
+        assert callable(fn) and fn.__name__ in dsp.__all__
+
+
+def test_header_carries_the_contract():
+    with open(os.path.join(ROOT, "include", "mavg.h")) as f:
+        h = f.read()
+    assert re.search(r"#define MAVG_ABI_VERSION 4\b", h)
+    assert re.search(r"#define MAVG_SOS_FP64_ONLY 1\b", h)
+    assert h.index("int mavg_biquad_plan") < h.index("int mavg_sos_run") < h.index("FIR filter (finite impulse response)")
+    block = h[h.index("Second-order sections:"):h.index("int mavg_sos_plan")]
+    for word in ("sos_none", "sos_tile", "sos_loop", "2^-23 |y_ref| + 2^-29 sum_j", "2^-24 sum_", "THE INTERMEDIATE IS fp32",
+                 "16 KiB", "2 <= sections <= 16", "launches = 1 + sections", "NOT yet tested past 2^32 samples",
+                 "NOT MEASURED", "0.86x at 16 KiB", "sum H_j * 8 B > 2 KiB", "must not be equal", "bits 4 .. 6", "MAVG_SOS_PLAN_UNALIGNED", "no memset node"):
+        assert word in block, word
+    with open(os.path.join(ROOT, "include", "mavg_debug.h")) as f:
+        assert re.search(r"^int mavg_debug_force_sos\(int path\);", f.read(), flags=re.M)
+
+
+IN, OUT, SIN, SOUT, WS = 1 << 20, 1 << 30, 1 << 24, 1 << 25, 1 << 26
+BIG = 1 << 40
+
+
+def _run(n, C=1, sos=B4, sections=None, dtype=F32, flags=0, din=IN, dout=OUT, sin=None, sout=None, ws=WS, ws_bytes=BIG,
+         coef="rows", path=None):
+    c = coefs(sos) if coef == "rows" else coef
+    return _lib.load(path).mavg_sos_run(din, dout, n, C, c, len(sos) if sections is None else sections, dtype, flags,
+                                        sin, sout, ws, ws_bytes, None)
+
+
+UNSTABLE = [B4[0], (1.0, 0.0, 0.0, -2.0, 1.0)]           # a pole pair on the circle
+NAN_ROW = [B4[0], (float("nan"), 0.0, 0.0, 0.0, 0.0)]
+
+
+@pytest.mark.parametrize("args,status", [
+    (dict(n=100, dtype=7), _lib.ERR_INVALID_ARG),                        # bad dtype
+    (dict(n=100, C=0), _lib.ERR_INVALID_ARG),                            # channels < 1
+    (dict(n=9, C=2), _lib.ERR_INVALID_ARG),                              # a partial frame
+    (dict(n=100, coef=None), _lib.ERR_INVALID_ARG),                      # NULL coef
+    (dict(n=100, sections=0), _lib.ERR_INVALID_ARG),                     # sections < 1
+    (dict(n=100, sections=-3), _lib.ERR_INVALID_ARG),
+    (dict(n=100, sos=UNSTABLE), _lib.ERR_INVALID_ARG),                   # every row is checked as the biquad's coef
+    (dict(n=100, sos=NAN_ROW), _lib.ERR_INVALID_ARG),
+    (dict(n=100, flags=2), _lib.ERR_INVALID_ARG),                        # flags other than 0 / MAVG_SOS_FP64_ONLY
+    (dict(n=100, flags=16), _lib.ERR_INVALID_ARG),                       # (the plan's view bits are the plan's)
+    (dict(n=100, flags=-1), _lib.ERR_INVALID_ARG),
+    (dict(n=100, sin=SIN, sout=SIN), _lib.ERR_INVALID_ARG),              # equal state pointers
+    (dict(n=100, din=0), _lib.ERR_INVALID_ARG),                          # a NULL view with work to do
+    (dict(n=100, dout=0), _lib.ERR_INVALID_ARG),
+    (dict(n=100, din=IN + 2), _lib.ERR_MISALIGNED),                      # fp32 input off 4 B
+    (dict(n=100, dtype=I16, din=IN + 1), _lib.ERR_MISALIGNED),           # int16 input off 2 B
+    (dict(n=100, dout=OUT + 2), _lib.ERR_MISALIGNED),                    # the fp32 output off 4 B
+    (dict(n=100, sin=SIN + 4), _lib.ERR_MISALIGNED),                     # a state pointer off 8 B
+    (dict(n=100, sout=SOUT + 4), _lib.ERR_MISALIGNED),
+    (dict(n=100, ws=WS + 8), _lib.ERR_MISALIGNED),                       # d_ws off 16 B
+    (dict(n=100, ws=0), _lib.ERR_WORKSPACE),                             # sos_tile needs its tables' workspace
+    (dict(n=100, ws_bytes=2 * SECTION_BYTES - 1), _lib.ERR_WORKSPACE),
+    (dict(n=99, C=3, ws_bytes=99 * 4), _lib.ERR_WORKSPACE),              # sos_loop: a buffer of 400 B and the strips' records
+    (dict(n=99, C=3, flags=1), _lib.ERR_UNSUPPORTED),                    # MAVG_SOS_FP64_ONLY refuses the loop
+    (dict(n=100, sos=B4 * 9, flags=1), _lib.ERR_UNSUPPORTED),            # 18 sections: past the fused maximum
+    (dict(n=0, din=0, dout=0, ws=0, ws_bytes=0), _lib.OK),               # nothing to do
+    (dict(n=0, dtype=9, din=0), _lib.ERR_INVALID_ARG),                   # validated before the no-op
+    (dict(n=0, sections=0, din=0), _lib.ERR_INVALID_ARG),
+    (dict(n=0, sin=SIN, sout=SIN), _lib.ERR_INVALID_ARG),
+    # past the one-launch limit: 256 threads per 4096-sample tile reach 2^32 work-items at 2^36 samples
+    (dict(n=1 << 36), _lib.ERR_UNSUPPORTED),
+    (dict(n=1 << 37, C=2, din=IN + 4), _lib.ERR_UNSUPPORTED),
+])
+def test_sos_run_validates_before_launch(args, status):
+    assert _run(**args) == status
+
+
+def test_one_section_is_the_biquad_unchanged():
+    """sos_none: the biquad's statuses, plan and workspace."""
+    one = [B4[1]]
+    for kw in (dict(), dict(channels=2, dtype=I16), dict(channels=3), dict(state=True, return_state=True, aligned=False)):
+        n = 30000
+        assert dsp.sos_plan(n, rows6(one), **kw) == "sos_none " + dsp.biquad_plan(n, one[0], **kw)
+        kw.pop("state", None), kw.pop("return_state", None), kw.pop("aligned", None)
+        assert dsp.sos_workspace_bytes(n, rows6(one), **kw) == dsp.biquad_workspace_bytes(n, one[0], **kw)
+    slow = [one_pole(1.0 - 2.0 ** -16)]                                  # the chain: a workspace of its own
+    assert "biquad_chain<" in dsp.sos_plan(1 << 20, rows6(slow))
+    assert dsp.sos_workspace_bytes(1 << 20, rows6(slow)) == dsp.biquad_workspace_bytes(1 << 20, slow[0]) > 0
+    assert dsp.sos_plan(1 << 20, rows6(slow), intermediate="fp64").startswith("sos_none ")   # no intermediate at all
+    assert dsp.sos_halo_frames(rows6(one)) == dsp.biquad_halo_frames(one[0])
+    assert _run(100, sos=one, ws=0, ws_bytes=0, din=0) == _lib.ERR_INVALID_ARG
+    assert _run(100, sos=one, sin=SIN, sout=SIN) == _lib.ERR_INVALID_ARG
+
+
+def test_halo_frames_is_the_sum_of_the_rows():
+    for sos in (B4, HP_PK, THREE, SEVEN):
+        assert dsp.sos_halo_frames(rows6(sos)) == sum(dsp.biquad_halo_frames(c) for c in sos)
+    out = ctypes.c_longlong(0)
+    lib = _lib.load()
+    assert lib.mavg_sos_halo_frames(coefs(B4), 2, None) == _lib.ERR_INVALID_ARG
+    assert lib.mavg_sos_halo_frames(None, 2, ctypes.byref(out)) == _lib.ERR_INVALID_ARG
+    assert lib.mavg_sos_halo_frames(coefs(B4), 0, ctypes.byref(out)) == _lib.ERR_INVALID_ARG
+    assert lib.mavg_sos_halo_frames(coefs(UNSTABLE), 2, ctypes.byref(out)) == _lib.ERR_INVALID_ARG
+
+
+def fields(plan):
+    return dict(kv.split("=", 1) for kv in plan.split() if "=" in kv)
+
+
+@pytest.mark.parametrize("dt", [F32, I16])
+@pytest.mark.parametrize("C", [1, 2])
+def test_the_tile_rule_on_both_sides_of_the_halo_boundary(dt, C):
+    """sum H_j at the limit runs sos_tile, one frame past it sos_loop; the layout at the limit is
+    inside the 64-KiB budget in both unit forms."""
+    lim = LIMIT[C]
+    assert lim * C * 8 == 16 * 1024
+    n = 3 * TILE_FRAMES[C] * C
+    F = 16 // (C * (4 if dt == F32 else 2))
+    for total in (lim - 1, lim):
+        sos = sections_with_halo(total, dsp.biquad_halo_frames, SEVEN)
+        assert dsp.sos_halo_frames(rows6(sos)) == total
+        for aligned in (True, False):
+            plan = dsp.sos_plan(n, rows6(sos), C, dt, aligned=aligned)
+            f = fields(plan)
+            assert plan.startswith(f"sos_tile<{NAME[dt]},C={C},F={F if aligned else 1}> sections=8 intermediate=f64 "), plan
+            hp = (total + 7) & ~7
+            assert f["halo_frames"] == str(total) and f["stage_halo"] == str(hp) and f["tile_frames"] == str(TILE_FRAMES[C])
+            assert int(f["lds"]) == (hp + TILE_FRAMES[C]) * C * 8 + 4 * C * 16 <= 64 * 1024, plan
+            assert f["grid"] == "3" and f["block"] == "256" and f["launches"] == "9" and f["ws"] == str(8 * SECTION_BYTES)
+        assert dsp.sos_workspace_bytes(n, rows6(sos), C, dt) == 8 * SECTION_BYTES
+        assert dsp.sos_plan(n, rows6(sos), C, dt, intermediate="fp64").startswith("sos_tile<")
+    for total in (lim + 1, lim + 2, 4 * lim):
+        sos = sections_with_halo(total, dsp.biquad_halo_frames, SEVEN)
+        plan = dsp.sos_plan(n, rows6(sos), C, dt)
+        assert plan.startswith(f"sos_loop dtype={NAME[dt]} C={C} sections=8 intermediate=f32 halo_frames={total} "), plan
+        assert dsp.sos_plan(n, rows6(sos), C, dt, aligned=False).startswith("sos_loop ")
+        with pytest.raises(dsp.MavgError) as e:
+            dsp.sos_plan(n, rows6(sos), C, dt, intermediate="fp64")
+        assert e.value.status == _lib.ERR_UNSUPPORTED
+        with pytest.raises(dsp.MavgError):
+            dsp.sos_workspace_bytes(n, rows6(sos), C, dt, intermediate="fp64")
+
+
+def test_the_measured_exception_int16_mono_two_sections():
+    """Past 256 frames (2 KiB of fp64) of total halo the rule gives int16 mono pairs to the loop;
+    MAVG_SOS_FP64_ONLY still runs them fused, and no other dtype, channel or section count moves."""
+    n = 3 * 4096
+    for total, tile in ((255, True), (256, True), (257, False), (2048, False)):
+        pair = sections_with_halo(total, dsp.biquad_halo_frames, [B4[0]])
+        plan = dsp.sos_plan(n, rows6(pair), 1, I16)
+        assert plan.startswith("sos_tile<i16,C=1,F=8> sections=2 " if tile else "sos_loop dtype=i16 C=1 sections=2 "), plan
+        assert dsp.sos_plan(n, rows6(pair), 1, I16, intermediate="fp64").startswith("sos_tile<i16,C=1,F=8> sections=2 ")
+        assert dsp.sos_workspace_bytes(n, rows6(pair), 1, I16, intermediate="fp64") == 2 * SECTION_BYTES
+        assert dsp.sos_plan(n, rows6(pair), 1, F32).startswith("sos_tile<f32,C=1,")
+        triple = pair + [COPY5]
+        assert dsp.sos_plan(n, rows6(triple), 1, I16).startswith("sos_tile<i16,C=1,F=8> sections=3 ")
+        if total <= 1024:
+            assert dsp.sos_plan(2 * n, rows6(pair), 2, I16).startswith("sos_tile<i16,C=2,")
+
+
+def test_the_section_count_at_and_past_its_maximum():
+    short = [one_pole(0.5)]                                              # a short halo: 16 of them fit
+    for S in (2, 3, MAX_SECTIONS - 1, MAX_SECTIONS):
+        plan = dsp.sos_plan(1 << 20, rows6(short * S), intermediate="fp64")
+        assert plan.startswith(f"sos_tile<f32,C=1,F=4> sections={S} ") and f" launches={S + 1}" in plan, plan
+        assert dsp.sos_workspace_bytes(1 << 20, rows6(short * S)) == (S * SECTION_BYTES + 15) // 16 * 16
+    for S in (MAX_SECTIONS + 1, 40):
+        plan = dsp.sos_plan(1 << 20, rows6(short * S))
+        assert plan.startswith(f"sos_loop dtype=f32 C=1 sections={S} intermediate=f32 ") and " buffers=2 " in plan, plan
+        with pytest.raises(dsp.MavgError) as e:
+            dsp.sos_plan(1 << 20, rows6(short * S), intermediate="fp64")
+        assert e.value.status == _lib.ERR_UNSUPPORTED
+
+
+@pytest.mark.parametrize("dt", [F32, I16])
+def test_two_against_three_channels_and_the_loop_workspace(dt):
+    frames = 3 * 4096 + 1234
+    for C in (1, 2):
+        assert dsp.sos_plan(frames * C, rows6(B4), C, dt).startswith("sos_tile<")
+    for C in (3, 5, 8):
+        for sos in (B4, THREE):
+            S = len(sos)
+            plan = dsp.sos_plan(frames * C, rows6(sos), C, dt)
+            assert plan.startswith(f"sos_loop dtype={NAME[dt]} C={C} sections={S} intermediate=f32 "), plan
+            f = fields(plan)
+            nbuf = 2 if S > 2 else 1
+            inner = max(dsp.biquad_workspace_bytes(frames * C, c, C, dt if j == 0 else F32) for j, c in enumerate(sos))
+            buf = (frames * C * 4 + 15) // 16 * 16
+            assert f["buffers"] == str(nbuf) and f["launches"] == str(3 * S)        # every section: the strip's three
+            assert int(f["ws"]) == nbuf * buf + inner == dsp.sos_workspace_bytes(frames * C, rows6(sos), C, dt)
+            with pytest.raises(dsp.MavgError) as e:
+                dsp.sos_plan(frames * C, rows6(sos), C, dt, intermediate="fp64")
+            assert e.value.status == _lib.ERR_UNSUPPORTED
+
+
+def test_plan_validates_and_shows_its_view_bits():
+    lib = _lib.load()
+    buf = ctypes.create_string_buffer(512)
+    c = coefs(B4)
+    assert lib.mavg_sos_plan(100, 1, c, 2, F32, 0, None, 0) == _lib.ERR_INVALID_ARG
+    assert lib.mavg_sos_plan(0, 1, c, 2, F32, 0, buf, len(buf)) == _lib.ERR_INVALID_ARG      # as mavg_plan
+    assert lib.mavg_sos_plan(100, 1, c, 0, F32, 0, buf, len(buf)) == _lib.ERR_INVALID_ARG
+    assert lib.mavg_sos_plan(100, 1, None, 2, F32, 0, buf, len(buf)) == _lib.ERR_INVALID_ARG
+    for flags in (2, 4, 8, 128, -1):
+        assert lib.mavg_sos_plan(100, 1, c, 2, F32, flags, buf, len(buf)) == _lib.ERR_INVALID_ARG
+    assert lib.mavg_sos_plan(1 << 36, 1, c, 2, F32, 0, buf, len(buf)) == _lib.ERR_UNSUPPORTED
+    for si in (False, True):
+        for so in (False, True):
+            for loop in (False, True):
+                C = 3 if loop else 1
+                assert f" state={int(si) + 2 * int(so)} " in dsp.sos_plan(9000 * C, rows6(B4), C, state=si, return_state=so)
+    assert ",F=1>" in dsp.sos_plan(9000, rows6(B4), aligned=False) and ",F=4>" in dsp.sos_plan(9000, rows6(B4))
+
+
+def test_wrappers_check_their_arguments():
+    with pytest.raises(ValueError):
+        dsp.sos_plan(100, [])
+    with pytest.raises(ValueError):
+        dsp.sos_plan(100, [[1.0, 0.0, 0.0, 0.0, 0.0]])                   # rows of 6
+    with pytest.raises(ValueError):
+        dsp.sos_plan(100, rows6(B4), intermediate="fp32")
+    with pytest.raises(ValueError):
+        dsp.sos_plan(100, rows6(UNSTABLE))
+    half = [[2.0 * v for v in r] for r in rows6(B4)]                     # a0 = 2: rows are normalised
+    assert dsp.sos_plan(9000, half) == dsp.sos_plan(9000, rows6(B4))
+
+
+FORCE_CHILD = r'''
+import sys
+sys.path.insert(0, "tests")
+import digital_signal_processsing_amd as dsp
+from digital_signal_processsing_amd import _lib
+from sos_ref import SEVEN, butter4_lp, one_pole, rows6, sections_with_halo
+lib = _lib.load(_lib.DEBUG_LIB_PATH)
+D = _lib.DEBUG_LIB_PATH
+plan = lambda *a, **k: dsp.sos_plan(*a, library=D, **k)
+wsb = lambda *a, **k: dsp.sos_workspace_bytes(*a, library=D, **k)
+def unsupported(fn, *a, **k):
+    try:
+        fn(*a, **k)
+        raise SystemExit(f"a forced path took a shape outside its range: {a} {k}")
+    except dsp.MavgError as e:
+        assert e.status == _lib.ERR_UNSUPPORTED
+assert lib.mavg_debug_force_sos(3) == _lib.ERR_INVALID_ARG and lib.mavg_debug_force_sos(-1) == _lib.ERR_INVALID_ARG
+b4 = rows6(butter4_lp(0.05))
+at = rows6(sections_with_halo(2048, lambda c: dsp.biquad_halo_frames(c, library=D), SEVEN))
+past = rows6(sections_with_halo(2049, lambda c: dsp.biquad_halo_frames(c, library=D), SEVEN))
+many = rows6([one_pole(0.5)] * 17)
+n = 1 << 20
+assert plan(n, b4).startswith("sos_tile<") and plan(n, past).startswith("sos_loop ") and plan(3 * n, b4, 3).startswith("sos_loop ")
+assert lib.mavg_debug_force_sos(_lib.SOS_LOOP) == _lib.OK
+for sos, C in ((b4, 1), (b4, 2), (at, 1), (past, 1), (b4, 3), (many, 1)):
+    assert plan(n * C, sos, C).startswith("sos_loop "), (len(sos), C)
+    assert wsb(n * C, sos, C) >= n * C * 4
+    unsupported(plan, n * C, sos, C, intermediate="fp64")       # MAVG_SOS_FP64_ONLY still refuses the loop
+    unsupported(wsb, n * C, sos, C, intermediate="fp64")
+assert plan(n, b4[:1]).startswith("sos_none ")                  # one section is never a cascade
+assert lib.mavg_debug_force_sos(_lib.SOS_TILE) == _lib.OK
+for sos, C in ((b4, 1), (b4, 2), (at, 1)):
+    assert plan(n * C, sos, C).startswith("sos_tile<"), (len(sos), C)
+    assert wsb(n * C, sos, C) == (len(sos) * 2712 + 15) // 16 * 16
+import ctypes
+for sos, C in ((past, 1), (at, 2), (b4, 3), (many, 1)):
+    unsupported(plan, n * C, sos, C)
+    unsupported(wsb, n * C, sos, C)
+    flat = [v for r in sos for v in dsp.biquad_coef(r)]
+    c = (ctypes.c_double * len(flat))(*flat)
+    assert lib.mavg_sos_run(1 << 20, 1 << 30, n * C, C, c, len(sos), _lib.F32, 0, None, None, 1 << 26, 1 << 40, None) == _lib.ERR_UNSUPPORTED
+assert lib.mavg_sos_run(0, 1 << 30, n, 1, c, len(many), _lib.F32, 0, None, None, 1 << 26, 1 << 40, None) == _lib.ERR_INVALID_ARG   # validated first
+assert lib.mavg_debug_force_sos(_lib.SOS_AUTO) == _lib.OK
+assert plan(n, b4).startswith("sos_tile<") and plan(n, past).startswith("sos_loop ")
+print("force hook ok")
+'''
+
+
+def test_force_hook_on_the_debug_build():
+    """The hook is process-wide state: exercised in a child process of its own."""
+    r = subprocess.run([sys.executable, "-c", FORCE_CHILD], cwd=ROOT, capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and "force hook ok" in r.stdout, (r.stdout[-2000:], r.stderr[-3000:])
+
+
+def test_every_instance_compiles_for_gfx950_without_scratch():
+    """The compiler's own resource report of csrc/mavg_sos.hip: the fused kernel in 8 instances (two
+    dtypes, one and two channels, two unit forms) and the set-up kernel; no scratch, and registers
+    that leave at least four waves per SIMD (three 48-KiB workgroups of four waves fit a CU)."""
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    if not os.path.exists(hipcc):
+        pytest.fail(f"{hipcc} not found: the resource report needs the compiler the library is built with")
+    r = subprocess.run([hipcc, "-O3", "-std=c++17", "--offload-arch=gfx950", "--cuda-device-only", "-c",
+                        "-Rpass-analysis=kernel-resource-usage", "-o", os.devnull, "mavg_sos.hip"],
+                       cwd=CSRC, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    names = re.findall(r"Function Name: (\S+)", r.stderr)
+    scratch = [int(v) for v in re.findall(r"ScratchSize \[bytes/lane\]: (\d+)", r.stderr)]
+    vgprs = [int(v) for v in re.findall(r" VGPRs: (\d+)", r.stderr)]
+    lds = [int(v) for v in re.findall(r"LDS Size \[bytes/block\]: (\d+)", r.stderr)]
+    assert len(names) == len(scratch) == len(vgprs) == len(lds) == 9, names
+    for kernel, count in (("sos_tile_kernel", 8), ("sos_setup_kernel", 1)):
+        assert sum(kernel in n for n in names) == count, (kernel, names)
+    assert all(s == 0 for s in scratch), list(zip(names, scratch))
+    assert all(v <= 128 for v in vgprs), list(zip(names, vgprs))         # 512 / 128: four waves per SIMD
+    assert all(b == 0 for b in lds), list(zip(names, lds))               # all LDS is dynamic (SosLds)
