@@ -977,7 +977,10 @@ int mavg_biquad_plan(size_t n_samples, int channels, const double coef[5], int d
  * takes any count) and past mavg_biquad_run's one-launch limit.
  *
  * Supported maximum.  Frame and sample indices are 64-bit wherever they are not
- * tile-local.  sos_tile is NOT yet tested past 2^32 samples.
+ * tile-local.  sos_tile (both unit forms, a state carried from an earlier chunk
+ * in and out, the full 16-KiB stage) and sos_loop (with one fp32 buffer and
+ * with two) are tested on 2^32 + 10^6-sample signals, every output
+ * (tests/test_gpu_bigsignal_filters.py).
  */
 #define MAVG_SOS_FP64_ONLY 1
 int mavg_sos_run(const void* d_in, float* d_out, size_t n_samples, int channels,

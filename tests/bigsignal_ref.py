@@ -25,7 +25,9 @@ And for the filters that are not built on it (second half of this file):
   chunked_fir_mismatches      exact fp64 sums of dyadic taps times int16-valued input, bit patterns
   chunked_ema_mismatches      fp64 decayed doubling over a chunk read with W frames of lead, d^W <= 2^-60,
   chunked_biquad_mismatches   the same on the state 2-vector, rho^W <= 2^-70; both against the bars
-                              of include/mavg.h, and both report the largest err / bar seen"""
+                              of include/mavg.h, and both report the largest err / bar seen
+  chunked_sos_mismatches      the biquad's column section by section, fp64 between the sections, the
+                              leads added up; the bar's absolute term comes from the caller"""
 import math
 
 import numpy as np
@@ -554,7 +556,53 @@ def chunked_biquad_mismatches(x, y, coef, C, G, M, chunk_frames, first_frame=0, 
                               2.0 ** -29 * G * M, stats, keep)
 
 
+def sos_lead(sos):
+    """W: the sum of the sections' biquad_lead -- section j spoils the first W_j frames of what it reads."""
+    return sum(biquad_lead(c) for c in sos)
+
+
+def _sos_column(col, rows, leads, nf):
+    """fp64 outputs of the last nf frames of a chunk's column through every row of ``rows``, each from
+    a zero state in front of the chunk: _biquad_column section by section, its doubling run to the
+    section's own lead; a section before the last returns every frame of its column, as fp64, and
+    nothing is rounded between sections."""
+    cur = col
+    for j, (c, W) in enumerate(zip(rows, leads)):
+        cur = _biquad_column(cur, c, W, nf if j == len(rows) - 1 else cur.numel())
+    return cur
+
+
+def chunked_sos_mismatches(x, y, sos, C, abs_term, chunk_frames, first_frame=0, stats=None, keep=None):
+    """chunked_biquad_mismatches for the cascade ``sos`` (rows b0 b1 b2 a1 a2, fp64 between the
+    sections): the bar is |y - ref| <= 2^-23 |ref| + abs_term, with abs_term the absolute term of
+    the header's bar as the caller computes it (tests/sos_ref.py: sos_abs_bar_at); the lead is
+    sos_lead(sos) frames -- in a chunk that does not start at frame 0, section j's first
+    biquad_lead(sos[j]) outputs lack what precedes the chunk, and the sections' shares add up."""
+    rows = [tuple(float(v) for v in c) if len(c) == 5 else None for c in sos]
+    if not rows or None in rows or not all(math.isfinite(v) for c in rows for v in c):
+        raise ValueError("sos: one or more rows of five finite numbers")
+    if y is not None and y.dtype != torch.float32:
+        raise ValueError("y must be float32")
+    leads = [biquad_lead(c) for c in rows]
+    return _chunked_recursive(x, y, C, abs_term, chunk_frames, first_frame, sum(leads),
+                              lambda col, nf: _sos_column(col, rows, leads, nf), abs_term, stats, keep)
+
+
 # The coefficients of the > 2^32-sample cases (tests/test_gpu_bigsignal_filters.py); the CPU tests of
 # this reference (tests/test_bigsignal_ref.py) measure it against the literal loops at the same ones.
 BIG_EMA_ALPHAS = (0.05, 0.01, 0.0051, 0.0026, 1e-4)
 BIG_BIQUADS = (("LP", 0.1, 0.707), ("LP", 0.002, 0.707), ("BP", 0.01, 4.0), ("HP", 0.0005, 0.7071))   # biquad_ref.rbj's kind, f, Q
+BIG_SOS = ("butter4", "three", "hp_pk", "limit8", "past9")     # big_sos's names
+
+
+def big_sos(name, halo_of):
+    """The rows (b0 b1 b2 a1 a2) of a named section set of the big cascade cases.  halo_of: the
+    library's mavg_biquad_halo_frames -- limit8 is tests/sos_ref.py's SEVEN and a one-pole low-pass
+    fitted so that the halos sum to stereo's limit of 1024 frames, past9 SEVEN, a one_pole(0.5) and
+    a fitted one-pole whose halos sum to one frame more."""
+    import sos_ref
+    if name == "limit8":
+        return sos_ref.sections_with_halo(1024, halo_of, sos_ref.SEVEN)
+    if name == "past9":
+        return sos_ref.sections_with_halo(1025, halo_of, sos_ref.SEVEN + [sos_ref.one_pole(0.5)])
+    return list({"butter4": sos_ref.butter4_lp(0.05), "three": sos_ref.THREE, "hp_pk": sos_ref.HP_PK}[name])

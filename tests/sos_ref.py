@@ -62,6 +62,17 @@ def sos_state_bar(sos, x, state=None, loop=False):
                      for j in range(len(sos))])
 
 
+def sos_abs_bar_at(sos, M, state=None, loop=False):
+    """sos_abs_bar from the level M = max |x| (and the state) instead of the signal: for a signal
+    that never comes to the host.  m_1 = max(M, |state_in[1]|), so a one-sample signal M gives it."""
+    return sos_abs_bar(sos, np.array([float(M)]), state, loop)
+
+
+def sos_state_bar_at(sos, M, state=None, loop=False):
+    """sos_state_bar from the level M = max |x| (and the state) instead of the signal."""
+    return sos_state_bar(sos, np.array([float(M)]), state, loop)
+
+
 def sos_min_halo(sos):
     """sum of the sections' smallest halos"""
     return sum(min_halo(c) for c in sos)

@@ -466,13 +466,19 @@ def _chunks_for(W):
     return (8192, 3001) + ((333,) if W <= 3001 else ())
 
 
-def _tamper_recursive(check, y):
+def _tamper_recursive(check, y, abs_term=None):
     """Bit 20 of an fp32 pattern is found at its index; one ulp (bit 0) is not.  One ulp is at most
     2^-23 |v| / m for a mantissa m in [1, 2); with the output's own half ulp, bit 0 stays inside the
-    bar's 2^-23 |ref| wherever m >= 1.5, so those are the samples flipped."""
+    bar's 2^-23 |ref| wherever m >= 1.5, so those are the samples flipped.  abs_term: the bar's
+    absolute term where an output can be smaller than it (a cascade whose sections cancel) -- bit 20
+    moves v = m 2^E, m in [0.5, 1), by 2^(E - 4), and only samples where that is more than twice the
+    bar are flipped."""
     n = y.numel()
-    m, _ = np.frexp(np.abs(y.numpy()))
-    cand = np.nonzero(m >= 0.75)[0]
+    m, e = np.frexp(np.abs(y.numpy()))
+    seen = m >= 0.75
+    if abs_term is not None:
+        seen &= np.ldexp(1.0, e - 4) > 2.0 * (abs_term + 2.0 ** -23 * np.abs(y.numpy()).astype(np.float64))
+    cand = np.nonzero(seen)[0]
     picks = [int(cand[0]), int(cand[cand.size // 2]), int(cand[-1])]
     assert picks[0] < n // 100 and picks[-1] > n - n // 100
     for i in picks:
@@ -542,3 +548,74 @@ def test_biquad_reference_against_the_literal_loop(oracle_mod, C, kind, f, Q, dt
     assert chunked_biquad_mismatches(xt, junk, coef, C, G, M, 3001, first_frame=ff) == (0, None)
     assert chunked_biquad_mismatches(xt, _flip(junk, ff * C, 20), coef, C, G, M, 3001, first_frame=ff) == (1, ff * C)
     _tamper_recursive(lambda t: chunked_biquad_mismatches(xt, t, coef, C, G, M, 3001), y)
+
+
+# ---- the cascade: second-order sections, fp64 between them ----
+from bigsignal_ref import BIG_SOS, big_sos, chunked_sos_mismatches, sos_lead  # noqa: E402
+
+import sos_ref  # noqa: E402
+
+
+@pytest.mark.parametrize("dt", ["i16", "f32"])
+@pytest.mark.parametrize("name", BIG_SOS)
+@pytest.mark.parametrize("C", (1, 2))
+def test_sos_reference_against_the_literal_loop(oracle_mod, C, name, dt):
+    """The section-by-section doubling reference against sos_ref.sos_ref (the biquad's recurrence
+    chained in fp64): the condition is 2^-35 of the bar's sum, sum_j G_j m_j prod_{i>j} G_i -- 1/64
+    of the bar's absolute term.  Measured over these cases (40 960 frames, every chunking): at most
+    7.2e-16 of that sum (int16 stereo, hp_pk); 3.2e-16 for the next worst set (butter4, int16),
+    5e-20 for limit8 and past9, whose sum is large against their outputs."""
+    import digital_signal_processsing_amd as dsp
+    sos = big_sos(name, dsp.biquad_halo_frames)
+    assert all(biquad_ref.domain_d(c) >= 2.0 ** -22 for c in sos)
+    x = _sig_dist(oracle_mod, C, dt, FR5, 2)
+    abs_term = sos_ref.sos_abs_bar_at(sos, biquad_ref.biquad_scale(x))
+    assert abs_term == sos_ref.sos_abs_bar(sos, x) and abs_term > 0.0
+    assert np.array_equal(sos_ref.sos_state_bar_at(sos, biquad_ref.biquad_scale(x)), sos_ref.sos_state_bar(sos, x))
+    total = abs_term * 2.0 ** 29                      # sum_j G_j m_j prod_{i>j} G_i
+    loop = sos_ref.sos_ref(x, sos, C)[0]
+    xt = torch.from_numpy(x.copy())
+    y = torch.from_numpy(loop.astype(np.float32))
+    W = sos_lead(sos)
+    assert W == sum(biquad_lead(c) for c in sos)
+    for chunk in _chunks_for(W):
+        keep = torch.full((x.size,), float("nan"), dtype=torch.float64)
+        stats = {}
+        assert chunked_sos_mismatches(xt, y, sos, C, abs_term, chunk, stats=stats, keep=keep) == (0, None), chunk
+        dev = float(np.abs(keep.numpy() - loop).max()) / total
+        print(f"sos {dt} C={C} {name} chunk={chunk}: |ref - loop| <= {dev:.2e} of the bar's sum, "
+              f"worst err / bar {stats['worst']:.3f}")
+        assert dev <= 2.0 ** -35, (chunk, dev)
+        assert 0.0 < stats["worst"] <= 1.0
+    ff = 12345
+    junk = y.clone()
+    junk[:ff * C] = 7.0
+    assert chunked_sos_mismatches(xt, junk, sos, C, abs_term, 3001, first_frame=ff) == (0, None)
+    assert chunked_sos_mismatches(xt, _flip(junk, ff * C, 20), sos, C, abs_term, 3001, first_frame=ff) == (1, ff * C)
+    _tamper_recursive(lambda t: chunked_sos_mismatches(xt, t, sos, C, abs_term, 3001), y, abs_term)
+
+
+def test_sos_reference_rejects_what_it_cannot_check():
+    xi = torch.zeros(64, dtype=torch.int16)
+    xf = torch.zeros(64, dtype=torch.float32)
+    ok = [sos_ref.COPY, sos_ref.one_pole(0.5)]
+    assert chunked_sos_mismatches(xi, xf, ok, 1, 1.0, 16) == (0, None)
+    assert chunked_sos_mismatches(xi, xf, ok, 2, 0.0, 16) == (0, None)
+    for bad in ([], [sos_ref.COPY, (1.0, 0.0, 0.0, 0.0)], [(1.0, 0.0, 0.0, 1.0, 0.0, 0.0)],
+                [(float("nan"), 0.0, 0.0, 0.0, 0.0)]):
+        with pytest.raises(ValueError):
+            chunked_sos_mismatches(xi, xf, bad, 1, 1.0, 16)                # rows that are not five numbers
+    with pytest.raises(ValueError):
+        chunked_sos_mismatches(xi, xi, ok, 1, 1.0, 16)                     # the output is fp32
+    with pytest.raises(ValueError):
+        chunked_sos_mismatches(xi, xf.double(), ok, 1, 1.0, 16)
+    with pytest.raises(ValueError):
+        chunked_sos_mismatches(xi, xf[:32], ok, 1, 1.0, 16)                # another size
+    with pytest.raises(ValueError):
+        chunked_sos_mismatches(xi, xf, ok, 5, 1.0, 16)                     # partial frame
+    with pytest.raises(ValueError):
+        chunked_sos_mismatches(xi, xf, ok, 1, float("nan"), 16)            # the bar's absolute term
+    with pytest.raises(ValueError):
+        chunked_sos_mismatches(xi, xf, ok, 1, -1.0, 16)
+    with pytest.raises(TypeError):
+        chunked_sos_mismatches(xf.double(), xf, ok, 1, 1.0, 16)            # the input is int16 or fp32

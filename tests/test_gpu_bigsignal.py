@@ -34,7 +34,10 @@ A case holds 2 x 8.6 GB (int16) or 2 x 17.2 GB (fp32) plus < 5 GiB of chunk
 temporaries (the second moment: the input and two fp32 views, up to 3 x 17.2
 GB; the filters' cases: an fp32 output per int16 input, 8.6 + 17.2 GB, and at
 most 3 x 17.2 GB for fp32 extrema with both outputs, plus up to 537 MB of
-records), and skips only when the (shared) device has less than that free."""
+records; the cascade's loop cases: the int16 input, the fp32 output and one or two
+fp32 buffers of the signal's size in the workspace, 8.6 + 2 x 17.2 GB and 8.6 +
+3 x 17.2 GB = 60.2 GB), and skips only when the (shared) device has less than
+that free."""
 import pytest
 
 from bigsignal_ref import chunked_mismatches

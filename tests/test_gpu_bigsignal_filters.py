@@ -1,5 +1,5 @@
 """Parity past 2^32 samples for the filters with kernels of their own: moving extrema, EMA,
-biquad and FIR.  One signal of 2^32 + ~10^6 samples (tests/test_gpu_bigsignal.py's sizes, views,
+biquad, the second-order-sections cascade and FIR.  One signal of 2^32 + ~10^6 samples (tests/test_gpu_bigsignal.py's sizes, views,
 guard bands and checksum) per dispatch path and unit form.  Each case checks, in this order,
   1. the plan text (a dispatch change cannot pass under an old id);
   2. the input, the history and a state passed in: unchanged;
@@ -13,11 +13,16 @@ guard bands and checksum) per dispatch path and unit form.  Each case checks, in
      CPU by tests/test_bigsignal_ref.py: extrema and FIR bit for bit, EMA and biquad against the
      bars of include/mavg.h, the largest err / bar printed;
   6. d_state_out, where the case asks for it, against the tail window's reference state.
+The cascade (mavg_sos_run) runs the same six through sos_ref.sos_ref, chunked_sos_mismatches and the
+header's two bars formed from the level M (sos_abs_bar_at, sos_state_bar_at; a streamed case's from
+the state actually passed in): sos_tile in both unit forms (element loads on the input side, the
+frame-unit stores on the output side), with a carried state, behind the full 16-KiB stage with a
+state_out, and sos_loop through one fp32 buffer of the signal's size and through two.
 int16 and every FIR case use generator dist 0 (FIR: taps m / 1024, so that every fp64 sum is exact
 and the contract's chain is bit for bit fl32 of it); fp32 extrema, EMA and biquad dist 2, the
 rounding-stress data.  M is the device maximum of |x|.
 
-The two `_streamed` cases are the header's streaming promise: a prefix of 2^16 frames of the
+The `_streamed` cases are the header's streaming promise: a prefix of 2^16 frames of the
 stream is filtered with a state_out, the remainder with that state as state_in, and the reference
 is the one-shot filter of the whole stream from a zero state, compared from frame 2^16 on.
 
@@ -230,6 +235,69 @@ class _Biquad:
         return chunked_biquad_mismatches(xall, yall, self.coef, C, self.G, M, STAT_CHUNK // C, first_frame, stats)
 
 
+class _Sos:
+    """The cascade: a named section set of bigsignal_ref.big_sos.  intermediate="fp64" is the
+    header's MAVG_SOS_FP64_ONLY (the tile or a refusal); loop: the case runs sos_loop and is held to
+    its bar.  The state has shape [S, C, 2], its bar is per section, and a state passed in enters
+    both bars through the levels m_j (state_in(), called with the host copy of a streamed case's)."""
+    name = "sos"
+
+    def __init__(self, set_name, intermediate="auto", loop=False):
+        import biquad_ref
+        import sos_ref
+        import digital_signal_processsing_amd as dsp
+        from bigsignal_ref import big_sos, sos_lead
+        self.rows, self.ref = big_sos(set_name, dsp.biquad_halo_frames), sos_ref
+        self.sos6, self.S = sos_ref.rows6(self.rows), len(self.rows)
+        self.intermediate, self.loop, self.sin = intermediate, loop, None
+        self.W = sos_lead(self.rows)
+        D = min(biquad_ref.domain_d(c) for c in self.rows)
+        self.what = (f"{set_name} sections={self.S} intermediate={intermediate} "
+                     f"G={[round(g, 3) for g in sos_ref.sos_gains(self.rows)]} D>={D:.2e}")
+        assert D >= 2.0 ** -22                                       # every row inside the promised domain
+
+    def plan(self, dsp, n, C, code, state, ret, aligned):
+        return dsp.sos_plan(n, self.sos6, C, code, state, ret, self.intermediate, aligned=aligned)
+
+    def workspace(self, dsp, n, C, code):
+        return dsp.sos_workspace_bytes(n, self.sos6, C, code, self.intermediate)
+
+    def check_workspace(self, ws_n, plan, n, tag):
+        """sos_tile: the sections' tables, exactly; sos_loop: one fp32 buffer of the signal's size (two
+        with three or more sections), each padded to 16 B, and the sections' own workspace."""
+        assert f" ws={ws_n} " in plan, tag
+        if plan.startswith("sos_tile<"):
+            assert not self.loop and ws_n == (self.S * 2712 + 15) // 16 * 16, tag
+        else:
+            nbuf = 2 if self.S > 2 else 1
+            assert self.loop and f" buffers={nbuf} " in plan and ws_n >= nbuf * ((4 * n + 15) // 16 * 16), tag
+
+    def state(self, torch, C, gpu, fill):
+        return torch.full((self.S, C, 2), fill, dtype=torch.float64, device=gpu)
+
+    def state_in(self, host_state):
+        self.sin = host_state.copy()
+
+    def run(self, dsp, x, y, C, **kw):
+        dsp.sosfilt_into(x, y, self.sos6, channels=C, intermediate=self.intermediate, **kw)
+
+    def host(self, xs, C):
+        return self.ref.sos_ref(xs, self.rows, C)
+
+    def bar(self, ref, M):
+        import numpy as np
+        return 2.0 ** -23 * np.abs(ref) + self.ref.sos_abs_bar_at(self.rows, M, self.sin, self.loop)
+
+    def state_bar(self, plan, M):
+        return self.ref.sos_state_bar_at(self.rows, M, self.sin, self.loop).reshape(self.S, 1, 1)
+
+    def chunked(self, xall, yall, C, M, first_frame, stats):
+        """(from frame 0 on -- a streamed case's prefix -- the state is zero and stays out of the bar)"""
+        from bigsignal_ref import chunked_sos_mismatches
+        abs_term = self.ref.sos_abs_bar_at(self.rows, M, self.sin if first_frame else None, self.loop)
+        return chunked_sos_mismatches(xall, yall, self.rows, C, abs_term, STAT_CHUNK // C, first_frame, stats)
+
+
 def _run_recursive(oracle_mod, gpu, filt, dt, C, want, in_off=0, out_off=0, streamed=False, state_out=False, tamper=None):
     import numpy as np
     import torch
@@ -245,7 +313,10 @@ def _run_recursive(oracle_mod, gpu, filt, dt, C, want, in_off=0, out_off=0, stre
     _check_plan(plan, want, tag)
     hf = PREFIX if streamed else 0
     ws_n = filt.workspace(dsp, n, C, code)
-    assert (ws_n > 0) == (not plan.startswith(f"{filt.name}_tile<")), tag
+    if hasattr(filt, "check_workspace"):      # a filter with a workspace on its tile too says what it expects
+        filt.check_workspace(ws_n, plan, n, tag)
+    else:
+        assert (ws_n > 0) == (not plan.startswith(f"{filt.name}_tile<")), tag
     _need(gpu, (n + hf * C) * esz + (n + 2 * hf * C + 2 * GUARD + 4) * 4 + ws_n + (5 << 30))
     ws = torch.empty(ws_n, dtype=torch.uint8, device=gpu) if ws_n else None
     xall, x, pre = _stream(gpu, dtype, n, hf * C, in_off, dist)
@@ -265,6 +336,8 @@ def _run_recursive(oracle_mod, gpu, filt, dt, C, want, in_off=0, out_off=0, stre
         torch.cuda.synchronize()
         sin_before = sin.clone()
         assert bool(torch.isfinite(sin).all()), tag
+        if hasattr(filt, "state_in"):         # a bar that depends on the state: formed from the actual one
+            filt.state_in(sin.cpu().numpy())
     sout = filt.state(torch, C, gpu, float("nan")) if ret else None
 
     filt.run(dsp, x, y, C, state=sin, state_out=sout, workspace=ws)
@@ -295,7 +368,7 @@ def _run_recursive(oracle_mod, gpu, filt, dt, C, want, in_off=0, out_off=0, stre
         if ret:
             dev = np.abs(sout.cpu().numpy().reshape(np.shape(tail_state)) - tail_state)
             sbar = filt.state_bar(plan, M)
-            print(f"  d_state_out: off by {float(dev.max()):.3e}, the bar {sbar:.3e}")
+            print(f"  d_state_out: off by {float(dev.max()):.3e}, the bar {float(np.max(sbar)):.3e}")
             assert (dev <= sbar).all(), f"d_state_out {sout.cpu().numpy()} against {tail_state}: {tag}"
     finally:
         del x, pre, xall, y, yall, ybuf, ws, ypre, sin, sout
@@ -341,6 +414,26 @@ BIQUAD_CASES = [
      ("biquad_chain<f32,C=1,F=4,U=2", " state=2 ", " records=2097641 ", " carry_chunk=2048 "), {"state_out": True}),
     ("biquad_strip_f32_c3_LP0.1", "f32", 3, ("LP", 0.1, 0.707), ("biquad_strip dtype=f32 C=3 L=64 ",), {}),
 ]
+# id, dtype, C, (section set, intermediate, held to the loop's bar), plan, keyword arguments
+SOS_CASES = [
+    # the header's streaming promise: the prefix's state_out carried in, a state_out again
+    ("sos_tile_f32_c1_butter4_streamed", "f32", 1, ("butter4", "auto", False),
+     ("sos_tile<f32,C=1,F=4>", " sections=2 ", " state=3 ", " launches=3"), {"streamed": True}),
+    # the full 16-KiB stage, the largest lds, a state_out from the last of 2 097 641 tiles
+    ("sos_tile_i16_c2_limit8", "i16", 2, ("limit8", "auto", False),
+     ("sos_tile<i16,C=2,F=4>", " halo_frames=1024 ", " sections=8 ", " lds=49280 ", " state=2 "), {"state_out": True}),
+    # an odd sample offset on stereo: the frame-unit form with element loads for the whole signal
+    ("sos_tile_f32_c2_three_frame_unit_eio", "f32", 2, ("three", "auto", False), ("sos_tile<f32,C=2,F=1>", " sections=3 "), {"in_off": 1}),
+    # the frame-unit output stores; the rule's exception run on the tile by MAVG_SOS_FP64_ONLY
+    ("sos_tile_i16_c1_hp_pk_frame_unit_out", "i16", 1, ("hp_pk", "fp64", False),
+     ("sos_tile<i16,C=1,F=1>", " sections=2 ", " halo_frames=661 "), {"out_off": 1}),
+    # the measured exception by the rule: int16 into fp32 through one buffer of more than 2^34 B
+    ("sos_loop_i16_c1_hp_pk_rule", "i16", 1, ("hp_pk", "auto", True),
+     ("sos_loop dtype=i16 C=1 sections=2", " halo_frames=661 ", " buffers=1 "), {}),
+    # both ping-pong buffers, the sections' own workspace behind 2 * buf
+    ("sos_loop_i16_c2_past9", "i16", 2, ("past9", "auto", True),
+     ("sos_loop dtype=i16 C=2 sections=9", " halo_frames=1025 ", " buffers=2 "), {"state_out": True}),
+]
 # id, dtype, C, taps, plan, keyword arguments
 FIR_CASES = [
     ("fir_tile_f32_c1_t33", "f32", 1, 33, ("fir_tile<f32,C=1,F=4,U=4,R=16>", " tile_frames=4096 "), {}),
@@ -366,6 +459,11 @@ def test_every_ema_output_past_2p32_samples(oracle_mod, gpu, name, dt, C, alpha,
 @pytest.mark.parametrize("name,dt,C,rbj,want,kw", BIQUAD_CASES, ids=[c[0] for c in BIQUAD_CASES])
 def test_every_biquad_output_past_2p32_samples(oracle_mod, gpu, name, dt, C, rbj, want, kw):
     _run_recursive(oracle_mod, gpu, _Biquad(*rbj), dt, C, want, **kw)
+
+
+@pytest.mark.parametrize("name,dt,C,sos,want,kw", SOS_CASES, ids=[c[0] for c in SOS_CASES])
+def test_every_sos_output_past_2p32_samples(oracle_mod, gpu, name, dt, C, sos, want, kw):
+    _run_recursive(oracle_mod, gpu, _Sos(*sos), dt, C, want, **kw)
 
 
 @pytest.mark.parametrize("name,dt,C,ntaps,want,kw", FIR_CASES, ids=[c[0] for c in FIR_CASES])
@@ -402,3 +500,7 @@ def test_ema_reference_sees_past_2p32(oracle_mod, gpu):
 
 def test_biquad_reference_sees_past_2p32(oracle_mod, gpu):
     _run_recursive(oracle_mod, gpu, _Biquad("LP", 0.1, 0.707), "i16", 1, "biquad_tile<i16,C=1,F=8,", tamper=_flip_two(20))
+
+
+def test_sos_reference_sees_past_2p32(oracle_mod, gpu):
+    _run_recursive(oracle_mod, gpu, _Sos("butter4", "fp64"), "i16", 1, ("sos_tile<i16,C=1,F=8>", " sections=2 "), tamper=_flip_two(20))

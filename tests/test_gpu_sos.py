@@ -1,13 +1,16 @@
 """mavg_sos_run on the GPU against the fp64 cascade (tests/sos_ref.py) and the header's two bars:
 sos_tile by rule and forced, sos_loop forced and past the halo limit, misaligned views, degenerate
 sizes, the state round trip, the worst-case input, the proof that the fused intermediate is fp64,
-graph capture, and an Inf that stays in its channel.  Shapes are about three tiles and a ragged tail."""
+graph capture, and an Inf that stays in its channel.  Shapes are about three tiles and a ragged tail;
+9, 16 and 17 sections, signals that end on, one frame before and one frame past a tile boundary, and
+a section without a halo between two with one have tests of their own."""
 import os
 
 import numpy as np
 import pytest
 
-from sos_ref import (COPY, DC_BLOCK, HP_PK, SEVEN, THIRD, THREE, TIMES3, butter4_lp, rows6, rule_takes_tile,
+from biquad_ref import rbj
+from sos_ref import (COPY, DC_BLOCK, HP_PK, SEVEN, THIRD, THREE, TIMES3, butter4_lp, one_pole, rows6, rule_takes_tile,
                      sections_with_halo, sos_bar, sos_ref, sos_state_bar, worst_case_input)
 
 pytestmark = pytest.mark.gpu
@@ -43,12 +46,18 @@ _sets = {}
 
 def section_set(name, C):
     """The section sets of the issue; `limit` / `past`: eight sections whose halos sum to the fused
-    kernel's limit for C channels, and to one frame more."""
+    kernel's limit for C channels, and to one frame more; `limit16`: the kernel's 16 sections at that
+    limit (SEVEN, eight one-pole low-passes and the fitted one); `nine`: its first nine rows;
+    `seventeen`: one section more than the kernel takes, far inside the halo limit."""
     if (name, C) not in _sets:
         halo = _dsp().biquad_halo_frames
         _sets[(name, C)] = {"butter4": lambda: B4, "hp_pk": lambda: HP_PK, "three": lambda: THREE,
                             "limit": lambda: sections_with_halo(LIMIT[C], halo, SEVEN),
-                            "past": lambda: sections_with_halo(LIMIT[C] + 1, halo, SEVEN)}[name]()
+                            "past": lambda: sections_with_halo(LIMIT[C] + 1, halo, SEVEN),
+                            "limit16": lambda: sections_with_halo(LIMIT[C], halo, SEVEN + [one_pole(0.5)] * 8),
+                            "nine": lambda: section_set("limit16", C)[:9],
+                            "seventeen": lambda: SEVEN + [one_pole(0.5)] * 10,
+                            "zero_halo_mid": lambda: [rbj("LP", 0.05, 0.7071), THIRD, rbj("HP", 0.05, 0.7071)]}[name]()
     return _sets[(name, C)]
 
 
@@ -162,7 +171,7 @@ def state_for(oracle, sos, kind, C):
 
 # ---- parity: by rule, forced tile, forced loop, each with its own bar ----
 @pytest.mark.parametrize("kind,C", KINDS)
-@pytest.mark.parametrize("name", ["butter4", "hp_pk", "three", "limit", "past"])
+@pytest.mark.parametrize("name", ["butter4", "hp_pk", "three", "limit", "past", "nine", "limit16"])
 def test_parity_by_rule_and_forced(gpu, oracle_mod, kind, C, name):
     dsp = _dsp()
     sos = section_set(name, C)
@@ -172,6 +181,10 @@ def test_parity_by_rule_and_forced(gpu, oracle_mod, kind, C, name):
     fits = name != "past"
     H = dsp.sos_halo_frames(rows6(sos))
     assert H <= LIMIT[C] if fits else H == LIMIT[C] + 1
+    if name in ("nine", "limit16"):           # 9 and 16 distinct starts and run lengths, 10 and 17 launches
+        assert len(sos) == (9 if name == "nine" else 16) and (name == "nine" or H == LIMIT[C])
+        plan = dsp.sos_plan(x.size, rows6(sos), C, _dt(kind))
+        assert f" sections={len(sos)} " in plan and plan.endswith(f" launches={len(sos) + 1}"), plan
     tile = fits and rule_takes_tile(kind == "i16", C, len(sos), H)      # (int16 mono pairs past 2 KiB: the loop)
     check(gpu, x, sos, C, key=key, family=TILE if tile else LOOP, loop=not tile)            # the rule
     s0 = state_for(oracle_mod, sos, kind, C)
@@ -245,6 +258,71 @@ def test_worst_case_input_in_front_of_the_second_tile(gpu, kind, M, name):
     with forced(1) as lib:
         _, _, ratio = check(gpu, x, sos, 1, library=lib, family=TILE)
     print(f"worst-case input, {name} {kind}: max err / bar = {ratio:.4f}")
+    # The same in the frame-unit form, in front of the third tile, and in stereo: channel 0 carries
+    # the pattern and channel 1 its negation one frame later, so a carry that slips from one channel
+    # into the other adds up instead of cancelling; each channel against its own mono reference.
+    dt = np.int16 if kind == "i16" else np.float32
+    for C, off_in, tiles in [(1, 1, 1), (1, 0, 2), (1, 1, 2), (2, 0, 1), (2, 1, 1), (2, 0, 2), (2, 1, 2)]:
+        sos = section_set(name, C)
+        TF = tile_frames(C)
+        t0 = tiles * TF
+        assert _dsp().sos_halo_frames(rows6(sos)) < TF
+        w = worst_case_input(sos, t0 + TF // 2 + 33, t0, M=M)
+        if C == 1:
+            x, ref = w.astype(dt), None
+        else:
+            x = np.stack([w, np.concatenate([[0.0], -w[:-1]])], axis=1).reshape(-1).astype(dt)
+            mono = [sos_ref(x[c::2], sos, 1) for c in range(2)]
+            ref = (np.stack([m[0] for m in mono], axis=1).reshape(-1), np.stack([m[1][:, 0, :] for m in mono], axis=1))
+        with forced(1) as lib:
+            _, _, ratio = check(gpu, x, sos, C, ref=ref, library=lib, family=TILE, off_in=off_in, form=1 if off_in else None)
+        print(f"worst-case input, {name} {kind} C={C} in+{off_in} in front of tile {tiles}: max err / bar = {ratio:.4f}")
+
+
+# ---- more sections than any other test runs: 9, 16 (parity above) and one past the kernel's count ----
+@pytest.mark.parametrize("kind,C", KINDS)
+def test_seventeen_sections_go_to_the_loop(gpu, oracle_mod, kind, C):
+    dsp = _dsp()
+    sos = section_set("seventeen", C)
+    frames = 3 * tile_frames(C) + 1234
+    x = signal(oracle_mod, kind, C, frames)
+    assert len(sos) == 17 and dsp.sos_halo_frames(rows6(sos)) <= LIMIT[C]      # the count alone keeps it off the tile
+    assert " sections=17 " in dsp.sos_plan(x.size, rows6(sos), C, _dt(kind))
+    check(gpu, x, sos, C, key=(kind, C, frames), family=LOOP, loop=True)
+    with pytest.raises(dsp.MavgError):
+        run(gpu, x, sos, C, intermediate="fp64")
+    with forced(1) as lib:
+        with pytest.raises(dsp.MavgError):
+            run(gpu, x, sos, C, library=lib)
+
+
+# ---- signals that end on a tile boundary, one frame short of it and one frame past it ----
+@pytest.mark.parametrize("kind,C", KINDS)
+@pytest.mark.parametrize("off_in", [0, 1])
+def test_tile_edge_lengths(gpu, oracle_mod, kind, C, off_in):
+    """TF, 2 TF and 3 TF frames: the last tile is full (the 16-B-unit form stores it whole).  TF + 1:
+    the last tile holds one frame, the last frame sits at stage index Hp and the state_out comes from
+    there.  2 TF - 1: one frame short.  The guards of run() catch a store past the end."""
+    sos = section_set("three", C)
+    TF = tile_frames(C)
+    s0 = state_for(oracle_mod, sos, kind, C)
+    whole = signal(oracle_mod, kind, C, 3 * TF, seed=5)
+    for frames in (TF, TF + 1, 2 * TF - 1, 2 * TF, 3 * TF):
+        check(gpu, whole[:frames * C], sos, C, state=s0, family=TILE, form=1 if off_in else None, off_in=off_in,
+              intermediate="fp64")
+
+
+# ---- a section without a halo between two with one: `start` does not advance ----
+@pytest.mark.parametrize("kind,C", [("f32", 1), ("i16", 2)])
+def test_a_zero_halo_section_in_the_middle(gpu, oracle_mod, kind, C):
+    dsp = _dsp()
+    sos = section_set("zero_halo_mid", C)
+    halos = [dsp.biquad_halo_frames(c) for c in sos]
+    assert halos[1] == 0 and halos[0] > 0 and halos[2] > 0, halos
+    frames = 3 * tile_frames(C) + 1234
+    x = signal(oracle_mod, kind, C, frames)
+    check(gpu, x, sos, C, key=(kind, C, frames), family=TILE, intermediate="fp64")
+    check(gpu, x, sos, C, state=state_for(oracle_mod, sos, kind, C), key=(kind, C, frames), family=TILE, intermediate="fp64")
 
 
 # ---- the intermediate is fp64 ----

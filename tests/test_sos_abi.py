@@ -73,7 +73,7 @@ def test_header_carries_the_contract():
     assert h.index("int mavg_biquad_plan") < h.index("int mavg_sos_run") < h.index("FIR filter (finite impulse response)")
     block = h[h.index("Second-order sections:"):h.index("int mavg_sos_plan")]
     for word in ("sos_none", "sos_tile", "sos_loop", "2^-23 |y_ref| + 2^-29 sum_j", "2^-24 sum_", "THE INTERMEDIATE IS fp32",
-                 "16 KiB", "2 <= sections <= 16", "launches = 1 + sections", "NOT yet tested past 2^32 samples",
+                 "16 KiB", "2 <= sections <= 16", "launches = 1 + sections", "are tested on 2^32 + 10^6-sample signals",
                  "NOT MEASURED", "0.86x at 16 KiB", "sum H_j * 8 B > 2 KiB", "must not be equal", "bits 4 .. 6", "MAVG_SOS_PLAN_UNALIGNED", "no memset node"):
         assert word in block, word
     with open(os.path.join(ROOT, "include", "mavg_debug.h")) as f:
